@@ -10,7 +10,12 @@ stable bucket partition of the probes (SURVEY.md 8(d) "sorted+matched").  Inputs
 FindMatches incl. extension, bucket replay and MatchList output) is reported
 beside it on BASELINE config 2 (4 x 10 Mbp, w15).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+ms_per_step).  --dump-outputs DIR then writes what the last timed step computed (the accepted
+probes, see dump_outputs) as DIR/<name>.npy.  --full adds everything else: K profiled steps
+(phase split, roofline of the dominant kernel), MUMs/s of the full FindMatches on C3, end to
+end, ParallelMemHash compat, the small MUMs/s configs and the CPU baselines.
 For N > 1 launch with torch.distributed.run (one rank per GPU): the same C3 input is
 split genome-block-per-rank and the seed stage runs sharded (libmems_amd/shard.py:
 keys per rank, RCCL all-to-all of key ranges, merge per key range), so the total
@@ -285,11 +290,55 @@ def run_e2e(mh, genomes, seed, reps: int = 2):
                         f"pinned buffers"}
 
 
+DUMP_SAMPLE = 2_000_000   # probes written by --dump-outputs (2 arrays x 8 B each: 32 MB)
+
+
+def dump_outputs(path: str, mh, st: dict, rank: int, world: int) -> None:
+    """--dump-outputs: what the last timed step left for its caller, as float64 .npy files.
+    The seed stage's product is the accepted probes in AddHashEntry order (MemHash.Probes:
+    hash bucket and smallest global seed-mer index of each probe's key group) and the counts
+    of mums_get_stats.  All P probes go into probe_totals (count and exact sums, split so every
+    term stays below 2^53); probe_buckets / probe_ref_index hold the probes at the sorted
+    indices probe_sample_index, a fixed seeded sample of min(P, DUMP_SAMPLE) of them."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+
+    def save(name, a):
+        np.save(os.path.join(path, name + sfx + ".npy"), np.asarray(a, dtype=np.float64))
+
+    save("seed_counts", [st["seedmers"], st["groups"], st["probes"], st["repeat_limit_groups"], st["key_bytes"]])
+    try:
+        buckets, ref = mh.Probes()
+    except lm.MumsError as e:
+        if e.code != lm.MUMS_E_UNSUPPORTED:
+            raise
+        # chunked runs (> 2^32 seed-mers) keep no probe table to export: the counts alone
+        progress(f"--dump-outputs: counts only ({e})")
+        return
+    P = len(buckets)
+    lo = ref & np.uint64((1 << 20) - 1)
+    hi = ref >> np.uint64(20)
+    save("probe_totals", [P, int(buckets.sum(dtype=np.uint64)), int(hi.sum(dtype=np.uint64)),
+                          int(lo.sum(dtype=np.uint64))])
+    if P > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(20240607).choice(P, DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(P)
+    save("probe_sample_index", idx)
+    save("probe_buckets", buckets[idx])
+    save("probe_ref_index", ref[idx])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled steps (phase split, roofline), the C3 "
+                         "FindMatches / end-to-end / compat MUMs/s, the small MUMs/s configs and the CPU baselines")
     ap.add_argument("--genomes", type=int, default=8)
     ap.add_argument("--length", type=int, default=100_000_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -307,6 +356,8 @@ def main():
                     help="c3 (default, the metric's config): 8 x 100 Mbp; c5: 2 x 3 Gbp (chunked mode on 1 GPU, "
                          "position-sharded genomes on N GPUs, N a multiple of 8)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
     if args.workload == "c5":
         args.genomes = 2
         if args.length == 100_000_000:   # not overridden: the config's 3 Gbp
@@ -427,23 +478,29 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
-    # after it, the same K steps with HIP events around every sort-pass launch (on the
-    # context's stream) for the dominant kernel's live duration and the phase split
-    progress(f"timed region done: {dt / args.steps * 1e3:.3f} ms/step; profiled steps")
-    mh.SetProfiling(True)
-    for _ in range(args.steps):
-        run()
-        st = stats()
-        ms_dom += st["ms_dominant"]
-        bytes_dom += st["dominant_bytes"]
-        launches += st["dominant_launches"]
-        for k in phase:
-            phase[k] += st[k]
-    mh.SetProfiling(False)
+    progress(f"timed region done: {dt / args.steps * 1e3:.3f} ms/step")
+    st = stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, mh, st, rank, world)
+        progress("outputs written")
+    if args.full:
+        # after it, the same K steps with HIP events around every sort-pass launch (on the
+        # context's stream) for the dominant kernel's live duration and the phase split
+        progress("profiled steps")
+        mh.SetProfiling(True)
+        for _ in range(args.steps):
+            run()
+            st = stats()
+            ms_dom += st["ms_dominant"]
+            bytes_dom += st["dominant_bytes"]
+            launches += st["dominant_launches"]
+            for k in phase:
+                phase[k] += st[k]
+        mh.SetProfiling(False)
     mums_c3 = None
     e2e_c3 = None
     compat_c3 = None
-    if world == 1 and args.workload == "c3" and not args.no_mums:
+    if args.full and world == 1 and args.workload == "c3" and not args.no_mums:
         # MUMs/s on the metric's own config: full FindMatches of the resident C3 genomes
         progress("C3 FindMatches")
         try:
@@ -488,7 +545,7 @@ def main():
                 compat_c3 = run_compat(local, genomes, seed)
             except Exception as e:  # report, never hide
                 compat_c3 = {"error": str(e)}
-    elif sharded and args.workload == "c3" and not args.no_mums and hasattr(stage, "run_find"):
+    elif args.full and sharded and args.workload == "c3" and not args.no_mums and hasattr(stage, "run_find"):
         # MUMs/s of the sharded FindMatches (mums_shard_run, all 8 steps: keys, record
         # all-to-allv, merge, bucket ranges, row all-to-allv, packed all-gather, chains + replay)
         # on the same split C3 input: total matches over the ranks / max-over-ranks time
@@ -606,6 +663,8 @@ def main():
             },
             "phase_ms_per_step": {k: round(v / args.steps, 3) for k, v in phase.items()},
         }
+        if not args.full:   # both come from the profiled steps
+            del out["roofline"], out["phase_ms_per_step"]
         if mums_c3 is not None:
             out["mums_c3"] = mums_c3
         if e2e_c3 is not None:
@@ -614,14 +673,14 @@ def main():
             out["mums_c3_compat"] = compat_c3
         if fallback is not None:
             out["exchange_fallback"] = fallback + " -> torch.distributed RCCL all_to_all (libmems_amd/shard.py)"
-        if not args.no_mums:
+        if args.full and not args.no_mums:
             progress("MUMs/s small configs")
             try:
                 out["mums"] = run_mums(local, dev, 0.01)
                 out["mums_iid"] = run_mums(local, dev, 1.0)
             except Exception as e:  # report, never hide
                 out["mums"] = {"error": str(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             progress("CPU baselines")
             out["cpu_baseline"] = cpu_baseline()
             if not args.no_mums:

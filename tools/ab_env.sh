@@ -12,7 +12,7 @@ for rep in 1 2; do
   for v in $VALS; do
     if [ "$v" = 0 ]; then unset $VAR; else export $VAR=$v; fi
     f=$(echo "$v" | tr '/.' '__')
-    timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 3 --no-cpu-baseline ${EXTRA_ARGS:---no-mums} \
+    timeout -k 10 300 python3 -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline ${EXTRA_ARGS:---no-mums} \
       > $OUT/v${f}_r$rep.json 2> $OUT/v${f}_r$rep.err || { echo "variant $v failed"; tail -20 $OUT/v${f}_r$rep.err; exit 11; }
     python3 - $OUT/v${f}_r$rep.json "$VAR=$v" <<'PY'
 import json, sys

@@ -11,7 +11,7 @@ VARS=${VARS:-"0 1 2 3"}
 for rep in 1 2; do
   for v in $VARS; do
     if [ "$v" = 0 ]; then unset MUMS_DEV_SORT3; else export MUMS_DEV_SORT3=$v; fi
-    timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 3 --no-cpu-baseline ${EXTRA_ARGS:---no-mums} \
+    timeout -k 10 300 python3 -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline ${EXTRA_ARGS:---no-mums} \
       > $OUT/v${v}_r$rep.json 2> $OUT/v${v}_r$rep.err || { echo "variant $v failed"; tail -20 $OUT/v${v}_r$rep.err; exit 11; }
     python3 - $OUT/v${v}_r$rep.json $v <<'PY'
 import json, sys
