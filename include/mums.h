@@ -111,7 +111,10 @@ int  mums_set_mask(mums_ctx* ctx, int masked, uint64_t seq_mask);
  * longest SML cut by MatchFinder::GetBreakpoint (MatchFinder.cpp:89-126), searched
  * one by one, thread tables merged by MergeTable (:105-121) -- so the MatchList is
  * the (patched) OpenMP reference's.  chunk_size 0 = the
- * reference's CHUNK_SIZE 200000 (:51).  enable=0 = serial MemHash (default). */
+ * reference's CHUNK_SIZE 200000 (:51).  enable=0 = serial MemHash (default).
+ * Repeat and enumeration tolerance (mums_set_params) apply inside every chunk's search as
+ * in MemHash (SetEnumerationTolerance / EnumerateMatches are inherited, MemHash.h:139,156-159);
+ * with enumeration tolerance > 1 the match log (mums_set_match_log) is MUMS_E_UNSUPPORTED. */
 int  mums_set_parallel_compat(mums_ctx* ctx, int enable, uint64_t chunk_size);
 /* PairwiseMatchFinder (PairwiseMatchFinder.h:23-33): a MemHash whose EnumerateMatches
  * (PairwiseMatchFinder.cpp:37-73) hashes every pair of genomes occurring once in a seed

@@ -1648,11 +1648,19 @@ int compat_keep_chunks(mums_ctx* ctx, uint32_t nch, int kbits, uint64_t* n_live,
     return MUMS_OK;
 }
 
+// (enumeration tolerance > 1: the odometer rows of the live chunk-major stream; below)
+template <typename K>
+int pairwise_rows(mums_ctx* ctx, uint64_t N, hipStream_t st);
+int sort_row_keys(mums_ctx* ctx, uint32_t* keys, uint64_t P, int bits, hipStream_t st);
+
 int run_pipeline_compat(mums_ctx* ctx, int stage) {
     hipStream_t st = ctx->stream;
     const int G = (int)ctx->genomes.size();
     const uint64_t N = ctx->N;
     MatchParams mp{ctx->repeat_tol, ctx->enum_tol, ctx->table_size, ctx->masked, ctx->seq_mask};
+    // enumeration tolerance > 1 (MemHash::EnumerateMatches is the one ParallelMemHash inherits):
+    // every (chunk, masked key) group's AddHashEntry calls as rows instead of the probe stage
+    const bool enum_rows = ctx->enum_tol > 1;
     GenomeTable& gt = ctx->gt;
     const int kbits = 2 * ctx->w + 1;
     int gbits = 0;
@@ -1675,9 +1683,9 @@ int run_pipeline_compat(mums_ctx* ctx, int stage) {
     HIPCHK(ctx->kB.ensure(N * 8 + 64));
     HIPCHK(ctx->vA.ensure(N * 4 + 64));
     HIPCHK(ctx->vB.ensure(N * 4 + 64));
-    HIPCHK(ctx->cval.ensure(N * 4 + 64));
+    HIPCHK(ctx->cval.ensure(enum_rows ? 2 * (N + 64) * 4 : N * 4 + 64));   // (enum_rows: row counts and offsets)
     HIPCHK(ctx->tiles.ensure(ntiles_groups * sizeof(SegTile) + 64));
-    size_t tmpb = std::max(scan_tmp_bytes(N), radix_tmp_bytes(N));
+    size_t tmpb = std::max(scan_tmp_bytes(N + 1), radix_tmp_bytes(N + 1));
     tmpb = std::max(tmpb, scan_tmp_bytes((uint64_t)ctx->table_size));
     HIPCHK(ctx->tmp.ensure(tmpb));
     ProbeSpace ps{};
@@ -1874,9 +1882,9 @@ int run_pipeline_compat(mums_ctx* ctx, int stage) {
     // falls back to the partition below.  It needs no key2 / index arrays, so it is taken only
     // where no later step reads them: no chunk cut (flag 4 screens runs above
     // MER_REPEAT_LIMIT), no rank split, match log or LogProgress.  MUMS_DEV_COMPAT_PART (read
-    // per call): the partition always.
+    // per call): the partition always.  The odometer rows (enum_rows) read key2 and the indices.
     uint64_t* drec = nullptr;
-    if (packed_sml && !reordered && N < (1ull << 32) && ctx->compat_ranks <= 1 && !ctx->match_log &&
+    if (packed_sml && !reordered && !enum_rows && N < (1ull << 32) && ctx->compat_ranks <= 1 && !ctx->match_log &&
         !ctx->progress_on && !getenv("MUMS_DEV_COMPAT_PAIRS") && !getenv("MUMS_DEV_COMPAT_GID_SCAN") &&
         !getenv("MUMS_DEV_COMPAT_PART")) {
         uint64_t* out = pstream.rec == ctx->recA.as<uint64_t>() ? ctx->recB.as<uint64_t>() : ctx->recA.as<uint64_t>();
@@ -1920,7 +1928,7 @@ int run_pipeline_compat(mums_ctx* ctx, int stage) {
     // pass as MER_REPEAT_LIMIT's candidate list, again after a chunk was cut;
     // MUMS_DEV_COMPAT_PAIRS (read per call): the (key2, index) pair kernels,
     // MUMS_DEV_COMPAT_GID_SCAN: group keys numbered by the scan
-    ctx->compat_rec = N < (1ull << 32) && !getenv("MUMS_DEV_COMPAT_PAIRS");
+    ctx->compat_rec = N < (1ull << 32) && !enum_rows && !getenv("MUMS_DEV_COMPAT_PAIRS");
     const bool gid_scan = getenv("MUMS_DEV_COMPAT_GID_SCAN") != nullptr;
     if (ctx->compat_rec) {
         HIPCHK(ctx->recA.ensure(N * 8 + 64));
@@ -1958,6 +1966,39 @@ int run_pipeline_compat(mums_ctx* ctx, int stage) {
                                   gid_scan, nullptr, nullptr, 0, st));
     if (ctx->progress_on && (rc = progress_compat(ctx, nch, hcs, st))) return rc;
     HIPCHK(hipEventRecord(ctx->ev[EV_SORT], st));
+    if (enum_rows) {
+        // the live chunk-major (key2, index) stream: a group is one (chunk, masked key) -- key2
+        // carries the chunk above the key -- with every genome's records in SML order (the tie
+        // replay above).  One row per AddHashEntry call in call order (pairwise.hip), their
+        // bucket order, then the tail's replay and MergeTable as for the probe rows.
+        rc = pairwise_rows<uint64_t>(ctx, n_live, st);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(ctx->ev[EV_GROUPS], st));
+        const uint64_t P = ctx->P;
+        ctx->probe_info = nullptr;
+        ctx->compat_pfirst.clear();
+        int tbits = 1;
+        while (tbits < 32 && ((uint64_t)1 << tbits) < (uint64_t)ctx->table_size) ++tbits;
+        if (P) {
+            HIPCHK(ctx->rowtmp.ensure((P + 64) * 16 + 8192));
+            uint32_t* bkt = (uint32_t*)ctx->rowtmp.p;
+            HIPCHK(launch_row_buckets(ctx->mprobe.as<int64_t>(), P, G, ctx->table_size, nullptr, 0, bkt, st));
+            if ((rc = sort_row_keys(ctx, bkt, P, tbits, st))) return rc;
+        }
+        HIPCHK(hipEventRecord(ctx->ev[EV_BUCKETS], st));
+        ctx->stage_done = MUMS_STAGE_SEEDS;
+        if (stage >= MUMS_STAGE_ALL) {
+            rc = find_tail(ctx, mp, ctx->packed.as<uint32_t>(), [&](MatProbes* v) {
+                v->rows = ctx->mprobe.as<int64_t>();
+                return MUMS_OK;
+            }, st);
+            if (rc) return rc;
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(&ctx->hc, dc, sizeof(DevCounters), hipMemcpyDeviceToHost));
+        fill_stats(ctx, N);
+        return MUMS_OK;
+    }
     SegTile* tiles = ctx->tiles.as<SegTile>();
     HIPCHK(launch_flat_tiles(n_live, tiles, st));
     if (ctx->compat_rec)
@@ -2226,8 +2267,13 @@ int mums_find_stage(mums_ctx* ctx, int stage) {
     const bool big = ctx->N >= 0xFFFFFFF0ull || getenv("MUMS_DEV_CHUNK_RECORDS") != nullptr;
     if (big && ctx->pcompat)
         return fail(ctx, MUMS_E_UNSUPPORTED, "more than 2^32 seed-mers: ParallelMemHash compat not supported");
-    if (ctx->pcompat && ctx->enum_tol > 1)
-        return fail(ctx, MUMS_E_UNSUPPORTED, "ParallelMemHash compat with enumeration tolerance > 1");
+    if (ctx->pcompat && ctx->pairwise && ctx->enum_tol > 1)   // (no reference class combines the two)
+        return fail(ctx, MUMS_E_UNSUPPORTED, "ParallelMemHash compat with PairwiseMatchFinder and enumeration tolerance > 1");
+    if (ctx->pcompat && ctx->enum_tol > 1 && ctx->match_log)
+        // the log's per-chunk order comes from the probe stage (compat_pfirst), which the
+        // odometer rows do not run
+        return fail(ctx, MUMS_E_UNSUPPORTED, "ParallelMemHash compat with enumeration tolerance > 1: the match log "
+                                             "(SetMatchLog) is not reproduced");
     if (!ctx->start_points.empty() && ctx->start_points.size() != ctx->genomes.size())   // MatchFinder.cpp:197-199
         return fail(ctx, MUMS_E_INVALID, "start points: one per sequence required");
     if (have_start_points(ctx) && ctx->pcompat)
@@ -2240,7 +2286,7 @@ int mums_find_stage(mums_ctx* ctx, int stage) {
     // the chunked mode may keep its (config-5-sized) tie workspace between seed-stage-only
     // calls; any other pipeline sizes its own
     if (!big && ctx->tiebuf_kept) release_tiebuf(ctx);
-    if ((ctx->pairwise || ctx->enum_tol > 1) && !big) return run_pipeline_pairwise(ctx, stage);
+    if ((ctx->pairwise || (ctx->enum_tol > 1 && !ctx->pcompat)) && !big) return run_pipeline_pairwise(ctx, stage);
     if (ctx->pcompat) return run_pipeline_compat(ctx, stage);
     return big ? run_pipeline_chunked(ctx, stage) : run_pipeline(ctx, stage);
 }
@@ -2598,8 +2644,11 @@ int mums::ctx_compat_layout(mums_ctx* ctx, uint32_t* first, uint32_t* nown, std:
     if (!ctx->shard) return fail(ctx, MUMS_E_INVALID, "no shard layout (mums_shard_layout)");
     if (ctx->slice)
         return fail(ctx, MUMS_E_UNSUPPORTED, "sharded ParallelMemHash compat: genome blocks only (no position slices)");
-    if (ctx->pairwise || ctx->enum_tol > 1)
-        return fail(ctx, MUMS_E_UNSUPPORTED, "ParallelMemHash compat with PairwiseMatchFinder / enumeration tolerance > 1");
+    if (ctx->pairwise)
+        return fail(ctx, MUMS_E_UNSUPPORTED, "ParallelMemHash compat with PairwiseMatchFinder");
+    if (ctx->enum_tol > 1 && ctx->match_log)   // (as on one context: mums_find_stage)
+        return fail(ctx, MUMS_E_UNSUPPORTED, "ParallelMemHash compat with enumeration tolerance > 1: the match log "
+                                             "(SetMatchLog) is not reproduced");
     if (!ctx->start_points.empty())
         return fail(ctx, MUMS_E_UNSUPPORTED, "start points (FindMatchesFromPosition) in the ParallelMemHash compat mode");
     const uint32_t nl = (uint32_t)ctx->genomes.size();
@@ -3116,6 +3165,7 @@ int shard_groups_chunked(mums_ctx* ctx, uint64_t* rec, const std::vector<uint32_
 // the sharded FindMatches reads its probe rows from ctx->rowsall (built once per merge /
 // restart) for a chunked merge and under enumeration tolerance > 1
 int enum_count_check(mums_ctx* ctx, hipStream_t st);   // (after sort_row_keys below)
+int enum_row_offsets(mums_ctx* ctx, const uint32_t* ncalls, uint32_t* off, uint64_t n, uint64_t* total, hipStream_t st);
 
 bool shard_rows_from_all(const mums_ctx* ctx) { return ctx->merge_chunked || ctx->enum_tol > 1 || ctx->pairwise; }
 
@@ -3153,21 +3203,16 @@ int shard_enum_rows(mums_ctx* ctx, hipStream_t st) {
     else if (ib33) HIPCHK(launch_enum_count(v64, n, ctx->gt, mp, ncalls, dc, st));
     else HIPCHK(launch_enum_count(v, n, ctx->gt, mp, ncalls, dc, st));
     HIPCHK(ctx->tmp.ensure(std::max(ctx->tmp.cap, scan_tmp_bytes(n + 1))));
-    uint32_t* total = &dc->nprobes;
     HIPCHK(ctx->rowtmp.ensure((n + 64) * 4 + 4096));
     uint32_t* off = (uint32_t*)ctx->rowtmp.p;
-    HIPCHK(hipMemcpyAsync(off, ncalls, n * 4, hipMemcpyDeviceToDevice, st));
-    HIPCHK(exclusive_scan_u32(off, n, ctx->tmp.p, total, st));
-    uint32_t P = 0;
-    HIPCHK(hipMemcpyAsync(&P, total, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (int rc = enum_count_check(ctx, st)) return rc;
-    HIPCHK(ctx->rowsall.ensure(((uint64_t)P + 1) * (G + 1) * 8));
+    uint64_t P = 0;
+    if (int rc = enum_row_offsets(ctx, ncalls, off, n, &P, st)) return rc;
+    HIPCHK(ctx->rowsall.ensure((P + 1) * (G + 1) * 8));
     int64_t* rows = ctx->rowsall.as<int64_t>();
     if (pw && ib33) HIPCHK(launch_pairwise_emit(v64, n, ctx->gt, ctx->L, ncalls, off, rows, st));
     else if (pw) HIPCHK(launch_pairwise_emit(v, n, ctx->gt, ctx->L, ncalls, off, rows, st));
-    else if (ib33) HIPCHK(launch_enum_emit(v64, n, ctx->gt, mp, ctx->L, ncalls, off, rows, st));
-    else HIPCHK(launch_enum_emit(v, n, ctx->gt, mp, ctx->L, ncalls, off, rows, st));
+    else if (ib33) HIPCHK(launch_enum_emit(v64, n, ctx->gt, mp, ctx->L, ncalls, off, P, rows, st));
+    else HIPCHK(launch_enum_emit(v, n, ctx->gt, mp, ctx->L, ncalls, off, P, rows, st));
     HIPCHK(hipStreamSynchronize(st));
     ctx->P = P;
     ctx->st.probes = P;
@@ -4122,6 +4167,26 @@ int enum_count_check(mums_ctx* ctx, hipStream_t st) {
     return MUMS_OK;
 }
 
+// after an enumeration / pair count over n stream positions: the per-head row counts (ncalls)
+// -> their 32-bit exclusive offsets for the emit (off; ctx->tmp holds scan_tmp_bytes(n + 1))
+// and *total = their sum in 64 bits.  Several groups below the 2^31 bound of one group can
+// wrap a 32-bit total: a sum the row stream does not hold fails here, before anything is
+// sized by it and before any emit.
+int enum_row_offsets(mums_ctx* ctx, const uint32_t* ncalls, uint32_t* off, uint64_t n, uint64_t* total, hipStream_t st) {
+    DevCounters* dc = ctx->counters.as<DevCounters>();
+    *total = 0;
+    HIPCHK(hipMemcpyAsync(off, ncalls, n * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(exclusive_scan_u32(off, n, ctx->tmp.p, &dc->nprobes, st));
+    HIPCHK(launch_sum_u64(ncalls, n, &dc->row_total, st));
+    unsigned long long sum = 0;
+    HIPCHK(hipMemcpyAsync(&sum, &dc->row_total, 8, hipMemcpyDeviceToHost, st));
+    if (int rc = enum_count_check(ctx, st)) return rc;   // (synchronizes the stream)
+    if (sum >= (1ull << 32) - 64)
+        return fail(ctx, MUMS_E_UNSUPPORTED, "more than 2^32 AddHashEntry calls (enumeration rows) in one FindMatches");
+    *total = sum;
+    return MUMS_OK;
+}
+
 // PairwiseMatchFinder::FindMatches (PairwiseMatchFinder.cpp:37-73 over MemHash): pair
 // path keys + sort, one probe row per single-copy genome pair of every group
 // (pairwise.hip), then the rows' buckets and the FindMatches tail.
@@ -4135,18 +4200,14 @@ int pairwise_rows(mums_ctx* ctx, uint64_t N, hipStream_t st) {
     const MatchParams mp{ctx->repeat_tol, ctx->enum_tol, ctx->table_size, ctx->masked, ctx->seq_mask};
     if (ctx->pairwise) HIPCHK(launch_pairwise_count<PairView<K>>(v, N, ctx->gt, npairs, dc, st));
     else HIPCHK(launch_enum_count<PairView<K>>(v, N, ctx->gt, mp, npairs, dc, st));
-    HIPCHK(hipMemcpyAsync(off, npairs, N * 4, hipMemcpyDeviceToDevice, st));
-    HIPCHK(exclusive_scan_u32(off, N, ctx->tmp.p, &dc->nprobes, st));
-    uint32_t P = 0;
-    HIPCHK(hipMemcpyAsync(&P, &dc->nprobes, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (int rc = enum_count_check(ctx, st)) return rc;
+    uint64_t P = 0;
+    if (int rc = enum_row_offsets(ctx, npairs, off, N, &P, st)) return rc;
     ctx->P = P;
-    HIPCHK(ctx->mprobe.ensure(((uint64_t)P + 1) * (size_t)(ctx->gt.G + 1) * 8));
+    HIPCHK(ctx->mprobe.ensure((P + 1) * (size_t)(ctx->gt.G + 1) * 8));
     if (ctx->pairwise)
         HIPCHK(launch_pairwise_emit<PairView<K>>(v, N, ctx->gt, ctx->L, npairs, off, ctx->mprobe.as<int64_t>(), st));
     else
-        HIPCHK(launch_enum_emit<PairView<K>>(v, N, ctx->gt, mp, ctx->L, npairs, off, ctx->mprobe.as<int64_t>(), st));
+        HIPCHK(launch_enum_emit<PairView<K>>(v, N, ctx->gt, mp, ctx->L, npairs, off, P, ctx->mprobe.as<int64_t>(), st));
     return MUMS_OK;
 }
 }  // extern "C++"
@@ -5181,24 +5242,19 @@ int run_pipeline_chunked(mums_ctx* ctx, int stage) {
             uint32_t* ncalls = (uint32_t*)(ei + (n_c + 32));
             uint32_t* off = ncalls + (n_c + 32);
             const PairView<uint64_t, uint64_t> pv{ek, ei};
-            uint32_t pc32 = 0;
+            uint64_t Pc = 0;
             if (n_c) {
                 HIPCHK(launch_chunk_pairs(ctx->sorted_rec, n_c, bstart, nbc + 1, (uint64_t)c * nbc, ek, ei, st));
                 if (ctx->pairwise) HIPCHK(launch_pairwise_count(pv, n_c, gt, ncalls, dc, st));
                 else HIPCHK(launch_enum_count(pv, n_c, gt, mp, ncalls, dc, st));
-                HIPCHK(hipMemcpyAsync(off, ncalls, n_c * 4, hipMemcpyDeviceToDevice, st));
-                HIPCHK(exclusive_scan_u32(off, n_c, ctx->tmp.p, &dc->nprobes, st));
-                HIPCHK(hipMemcpyAsync(&pc32, &dc->nprobes, 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                if ((rc = enum_count_check(ctx, st))) return rc;
+                if ((rc = enum_row_offsets(ctx, ncalls, off, n_c, &Pc, st))) return rc;
             }
-            const uint64_t Pc = pc32;
             if (stage >= MUMS_STAGE_ALL && Pc) {
                 rc = grow_rows(Pc, c);
                 if (rc) return rc;
                 int64_t* rows = (int64_t*)((char*)ctx->rowsall.p + P_total * Wrow);
                 if (ctx->pairwise) HIPCHK(launch_pairwise_emit(pv, n_c, gt, ctx->L, ncalls, off, rows, st));
-                else HIPCHK(launch_enum_emit(pv, n_c, gt, mp, ctx->L, ncalls, off, rows, st));
+                else HIPCHK(launch_enum_emit(pv, n_c, gt, mp, ctx->L, ncalls, off, Pc, rows, st));
             }
             HIPCHK(hipEventRecord(ctx->ev[EV_GROUPS], st));
             HIPCHK(hipEventRecord(ctx->ev[EV_BUCKETS], st));

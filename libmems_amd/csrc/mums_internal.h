@@ -127,6 +127,7 @@ struct DevCounters {
     unsigned long long short_items;   // walks it took from the queue
     unsigned long long short_wins;
     unsigned long long log_n;         // insertion events recorded for SetMatchLog (replay.hip)
+    unsigned long long row_total;     // enumeration rows of one count, summed in 64 bits (launch_sum_u64)
 };
 
 // A tile of the segmented (per-MSD-bucket) sort/group passes.  Tiles never
@@ -210,6 +211,8 @@ hipError_t launch_keys_of_genome(const SeedSpec& ss, const uint32_t* d_words, ui
 // scan.hip: exclusive scan of n uint32 values in place; d_tmp needs scan_tmp_bytes(n)
 size_t scan_tmp_bytes(uint64_t n);
 hipError_t exclusive_scan_u32(uint32_t* d_data, uint64_t n, void* d_tmp, uint32_t* d_total, hipStream_t st);
+// scan.hip: *d_total = the sum of n uint32 values in 64 bits (what a 32-bit scan total wraps)
+hipError_t launch_sum_u64(const uint32_t* d_data, uint64_t n, unsigned long long* d_total, hipStream_t st);
 
 // radix_sort.hip: stable LSD radix sort of keys over bit range [0, bits); values are
 // the implicit indices 0..n-1 when vals_in == nullptr.  ev_ds (optional): 2 events per
@@ -451,14 +454,15 @@ hipError_t launch_pairwise_emit(View v, uint64_t N, const GenomeTable& gt, int L
 hipError_t launch_digit_totals(const uint32_t* hist, uint32_t ndigits, uint32_t T, unsigned long long* out,
                                hipStream_t st);
 
-// MemHash with enumeration tolerance > 1 (any: slot kernels up to 8, group walks above):
-// AddHashEntry calls per group, their rows
+// MemHash with enumeration tolerance > 1 (any: slot kernels up to 8, above them a group walk
+// per output row): AddHashEntry calls per group, their rows (P = all of them: the sum of
+// ncalls, off = its exclusive scan)
 template <typename View>
 hipError_t launch_enum_count(View v, uint64_t N, const GenomeTable& gt, const MatchParams& mp, uint32_t* ncalls,
                              void* ctr, hipStream_t st);
 template <typename View>
 hipError_t launch_enum_emit(View v, uint64_t N, const GenomeTable& gt, const MatchParams& mp, int L,
-                            const uint32_t* ncalls, const uint32_t* off, int64_t* rows, hipStream_t st);
+                            const uint32_t* ncalls, const uint32_t* off, uint64_t P, int64_t* rows, hipStream_t st);
 
 // pairwise.hip: a chunked-mode chunk (RecViewT<33>, nb + 1 bucket starts, bucket j = implicit
 // digit digit0 + j) as (full ckey, 64-bit index) pairs for the enumeration kernels

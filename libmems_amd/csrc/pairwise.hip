@@ -106,7 +106,7 @@ __global__ void pw_emit_kernel(View v, uint64_t N, GenomeTable gt, int L, const 
 }
 
 // ---- enumeration tolerance > 1 -------------------------------------------------------
-constexpr int kEnumMax = 8;   // enum_tol bound of the slot kernels (per-genome record slots); above: the walk kernels
+constexpr int kEnumMax = 8;   // enum_tol bound of the slot kernels (per-genome record slots); above: the walk count, the by-row emit
 
 // MemHash::EnumerateMatches over the group at head h (per genome in SML order): per genome the
 // first min(count, enum_tol) records; rejected (false) when a genome has more than
@@ -233,11 +233,11 @@ __global__ void en_emit_kernel(View v, uint64_t N, GenomeTable gt, MatchParams m
 
 // ---- enumeration tolerance above kEnumMax ---------------------------------------------
 // Same AddHashEntry calls as en_count / en_emit, without per-genome record slots: the count
-// keeps c[g] = min(count, enum_tol) only, and each odometer combination re-walks the group,
+// keeps c[g] = min(count, enum_tol) only, and every odometer combination walks the group,
 // taking the q[g]-th record of genome g (a genome's records in the group are in its
 // SortedMerList order, so its first c[g] records are the ones MemHash::EnumerateMatches
-// lists, MemHash.cpp:146-152).  O(group size) per AddHashEntry call: the rare large
-// tolerances pay for the walk, enum_tol <= kEnumMax keeps the slot kernels above.
+// lists, MemHash.cpp:146-152).  O(group size) per AddHashEntry call, one lane per call
+// (en_emit_rows_kernel); enum_tol <= kEnumMax keeps the slot kernels above.
 template <int MG, typename View>
 __device__ bool en_tally(const View& v, uint64_t h, uint64_t N, const GenomeTable& gt, const MatchParams& mp,
                          uint32_t (&c)[MG], uint32_t* size) {
@@ -273,58 +273,65 @@ __global__ void en_count_walk_kernel(View v, uint64_t N, GenomeTable gt, MatchPa
     ncalls[i] = k;
 }
 
+// One lane per output row (AddHashEntry call).  Row r belongs to the last head i with
+// off[i] <= r: entries without calls share their successor's offset, so an upper bound over
+// the scanned offsets lands on a head with ncalls > 0.  The lane tallies the group, decodes
+// t = r - off[i] into the per-genome choices (the last genome varies fastest), walks the
+// group once more to take the q[g]-th record of each genome and writes its own row:
+// consecutive lanes write consecutive (G+1) * 8-byte rows.  P = all rows (the scan total).
 template <int MG, typename View>
-__global__ void en_emit_walk_kernel(View v, uint64_t N, GenomeTable gt, MatchParams mp, int L,
-                                    const uint32_t* __restrict__ ncalls, const uint32_t* __restrict__ off,
-                                    int64_t* __restrict__ rows) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N || ncalls[i] == 0) return;
+__global__ void en_emit_rows_kernel(View v, uint64_t N, GenomeTable gt, MatchParams mp, int L,
+                                    const uint32_t* __restrict__ off, uint64_t P, int64_t* __restrict__ rows) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= P) return;
+    uint64_t lo = 0, hi = N;   // off[lo] <= r < off[hi] (off[0] = 0, off[N] = P)
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if ((uint64_t)off[mid] <= r) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t i = lo;
     const int G = gt.G;
     uint32_t c[MG], size = 0;
     (void)en_tally<MG>(v, i, N, gt, mp, c, &size);
     bool two;
-    const uint64_t K = en_calls<MG>(c, G, mp, &two);
-    const uint64_t k0 = v.gkey(i);
-    uint64_t o = off[i];
-    for (uint64_t t = 0; t < K; ++t) {
-        uint32_t q[MG];   // the record of each genome this combination takes (two: every kept one)
-        int64_t sv[MG];
-        uint32_t pv[MG];
-        for (int g = 0; g < G; ++g) { sv[g] = 0; pv[g] = 0; q[g] = 0; }
-        if (!two) {   // odometer: the last genome varies fastest (MatchFinder.cpp:371-390)
-            uint64_t rem = t;
-            for (int g = G - 1; g >= 0; --g) {
-                if (!c[g]) continue;
-                q[g] = (uint32_t)(rem % c[g]);
-                rem /= c[g];
-            }
+    (void)en_calls<MG>(c, G, mp, &two);
+    uint32_t q[MG];   // the record of each genome this combination takes (two: every kept one)
+    int64_t sv[MG];
+    uint32_t pv[MG], seen[MG];
+    for (int g = 0; g < G; ++g) { sv[g] = 0; pv[g] = 0; q[g] = 0; seen[g] = 0; }
+    if (!two) {   // odometer: the last genome varies fastest (MatchFinder.cpp:371-390)
+        uint64_t rem = r - off[i];
+        for (int g = G - 1; g >= 0; --g) {
+            if (!c[g]) continue;
+            q[g] = (uint32_t)(rem % c[g]);
+            rem /= c[g];
         }
-        uint32_t seen[MG];
-        for (int g = 0; g < G; ++g) seen[g] = 0;
-        for (uint64_t j = i; j < N && v.gkey(j) == k0; ++j) {
-            const RecFields r = v.get(j);
-            const int g = genome_of(gt, r.idx);
-            const uint32_t s = seen[g]++;
-            if (s >= c[g]) continue;   // past the genome's first enum_tol records
-            if (two || s == q[g]) {    // (two: the list's records, the later one of a genome wins as in en_emit)
-                sv[g] = (int64_t)(r.idx - gt.base[g]) + 1;
-                pv[g] = r.par;
-            }
-        }
-        // SetDirection (MemHash.cpp:189-203) + CalculateOffset (MatchHashEntry.cpp:141-160)
-        int ref = -1;
-        for (int g = 0; g < G && ref < 0; ++g)
-            if (sv[g] != 0) ref = g;
-        int64_t offset = 0;
-        for (int g = ref + 1; g < G; ++g) {
-            if (sv[g] == 0) continue;
-            if (pv[g] != pv[ref]) sv[g] = -sv[g];
-            offset += sv[g] - sv[ref] - (sv[g] < 0 ? (int64_t)L : 0);
-        }
-        int64_t* row = rows + (o + t) * (uint64_t)(G + 1);
-        for (int g = 0; g < G; ++g) row[g] = sv[g];
-        row[G] = offset;
     }
+    const uint64_t k0 = v.gkey(i);
+    for (uint64_t j = i; j < N && v.gkey(j) == k0; ++j) {
+        const RecFields rec = v.get(j);
+        const int g = genome_of(gt, rec.idx);
+        const uint32_t s = seen[g]++;
+        if (s >= c[g]) continue;   // past the genome's first enum_tol records
+        if (two || s == q[g]) {    // (two: the list's records, the later one of a genome wins as in en_emit)
+            sv[g] = (int64_t)(rec.idx - gt.base[g]) + 1;
+            pv[g] = rec.par;
+        }
+    }
+    // SetDirection (MemHash.cpp:189-203) + CalculateOffset (MatchHashEntry.cpp:141-160)
+    int ref = -1;
+    for (int g = 0; g < G && ref < 0; ++g)
+        if (sv[g] != 0) ref = g;
+    int64_t offset = 0;
+    for (int g = ref + 1; g < G; ++g) {
+        if (sv[g] == 0) continue;
+        if (pv[g] != pv[ref]) sv[g] = -sv[g];
+        offset += sv[g] - sv[ref] - (sv[g] < 0 ? (int64_t)L : 0);
+    }
+    int64_t* row = rows + r * (uint64_t)(G + 1);
+    for (int g = 0; g < G; ++g) row[g] = sv[g];
+    row[G] = offset;
 }
 
 inline dim3 grid_of(uint64_t n) { return dim3((unsigned)((n + 255) / 256)); }
@@ -371,13 +378,14 @@ hipError_t launch_enum_count(View v, uint64_t N, const GenomeTable& gt, const Ma
 
 template <typename View>
 hipError_t launch_enum_emit(View v, uint64_t N, const GenomeTable& gt, const MatchParams& mp, int L,
-                            const uint32_t* ncalls, const uint32_t* off, int64_t* rows, hipStream_t st) {
-    if (N == 0) return hipSuccess;
+                            const uint32_t* ncalls, const uint32_t* off, uint64_t P, int64_t* rows, hipStream_t st) {
+    if (N == 0 || P == 0) return hipSuccess;
     const bool walk = mp.enum_tol > (uint32_t)kEnumMax;
+    if (walk && (P + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;   // (rows of one launch: < 2^39)
     if (gt.G > 32 && walk)
-        hipLaunchKernelGGL((en_emit_walk_kernel<64, View>), grid_of(N), dim3(256), 0, st, v, N, gt, mp, L, ncalls, off, rows);
+        hipLaunchKernelGGL((en_emit_rows_kernel<64, View>), grid_of(P), dim3(256), 0, st, v, N, gt, mp, L, off, P, rows);
     else if (walk)
-        hipLaunchKernelGGL((en_emit_walk_kernel<32, View>), grid_of(N), dim3(256), 0, st, v, N, gt, mp, L, ncalls, off, rows);
+        hipLaunchKernelGGL((en_emit_rows_kernel<32, View>), grid_of(P), dim3(256), 0, st, v, N, gt, mp, L, off, P, rows);
     else if (gt.G > 32)
         hipLaunchKernelGGL((en_emit_kernel<64, View>), grid_of(N), dim3(256), 0, st, v, N, gt, mp, L, ncalls, off, rows);
     else
@@ -392,7 +400,7 @@ hipError_t launch_enum_emit(View v, uint64_t N, const GenomeTable& gt, const Mat
     template hipError_t launch_enum_count<V>(V, uint64_t, const GenomeTable&, const MatchParams&, uint32_t*, void*, \
                                              hipStream_t);                                                          \
     template hipError_t launch_enum_emit<V>(V, uint64_t, const GenomeTable&, const MatchParams&, int,               \
-                                            const uint32_t*, const uint32_t*, int64_t*, hipStream_t);
+                                            const uint32_t*, const uint32_t*, uint64_t, int64_t*, hipStream_t);
 MUMS_INST_PW(PairView<uint32_t>)
 MUMS_INST_PW(PairView<uint64_t>)
 typedef PairView<uint64_t, uint64_t> PairView64;

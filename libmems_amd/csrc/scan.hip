@@ -6,6 +6,8 @@
 // Partial sums are scanned recursively, so any n < 2^32 works.
 #include "mums_internal.h"
 
+#include <algorithm>
+
 namespace mums {
 
 namespace {
@@ -119,6 +121,16 @@ __global__ __launch_bounds__(kBlock) void scan_small_kernel(uint32_t* __restrict
     if (total_out && threadIdx.x == 0) *total_out = tot;
 }
 
+// 64-bit sum: grid-stride partial sums, a wave64 shuffle reduction, one atomic per wave
+__global__ __launch_bounds__(kBlock) void sum_u64_kernel(const uint32_t* __restrict__ in, uint64_t n,
+                                                         unsigned long long* __restrict__ total) {
+    unsigned long long s = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) s += in[i];
+    #pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(total, s);
+}
+
 uint64_t nblk(uint64_t n) { return (n + kScanTile - 1) / kScanTile; }
 
 }  // namespace
@@ -149,6 +161,14 @@ hipError_t exclusive_scan_u32(uint32_t* d_data, uint64_t n, void* d_tmp, uint32_
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(scan_down_kernel, dim3((unsigned)nb), dim3(kBlock), 0, st, d_data, n, partials, d_total,
                        nb);
+    return hipGetLastError();
+}
+
+hipError_t launch_sum_u64(const uint32_t* d_data, uint64_t n, unsigned long long* d_total, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(d_total, 0, sizeof(unsigned long long), st);
+    if (e != hipSuccess || n == 0) return e;
+    const uint64_t nb = std::min<uint64_t>((n + kBlock - 1) / kBlock, 1024);
+    hipLaunchKernelGGL(sum_u64_kernel, dim3((unsigned)nb), dim3(kBlock), 0, st, d_data, n, d_total);
     return hipGetLastError();
 }
 
