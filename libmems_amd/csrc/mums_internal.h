@@ -144,24 +144,38 @@ struct SegTile {
     uint32_t order;     // onesweep claim order: the c-th claimed block sorts tile tiles[c].order
 };
 
-// Stable wave64 "match any" on a kBits-bit digit: *peers_out = popcount of the lanes
-// (valid ones) holding the same digit, returned value = how many of them sit in lower
-// lanes.  Per digit bit: a 1-bit signed extract (0 / all ones), one ballot, and
-// peers &= ~(X ^ ext) on each 32-bit half (one v_bitop3 each); the rank is two mbcnt ops.
+// Stable wave64 "match any" on the low kBits bits of a digit (the caller passes the live bit
+// count; higher bits must be equal in every lane): *peers_out = popcount of the lanes (valid
+// ones) holding the same digit, returned value = how many of them sit in lower lanes.  Four
+// VALU per digit bit: a 1-bit signed extract (0 / all ones), one compare of that mask against
+// zero whose lane mask is the ballot, and peers &= ~(X ^ ext) on each 32-bit half (one
+// v_bitop3 each); the rank is two mbcnt ops.  (pl, ph) = the lanes that take part.
 template <int kBits>
-__device__ __forceinline__ uint32_t wave_match_rank(uint32_t dg, bool valid, uint32_t* peers_out) {
-    const uint64_t v = __ballot(valid);
-    uint32_t pl = (uint32_t)v, ph = (uint32_t)(v >> 32);
+__device__ __forceinline__ uint32_t wave_match_rank_from(uint32_t dg, uint32_t pl, uint32_t ph, uint32_t* peers_out) {
     #pragma unroll
     for (int b = 0; b < kBits; ++b) {
         const uint32_t ms = (uint32_t)__builtin_amdgcn_sbfe((int32_t)dg, b, 1);   // all ones when set
-        const uint64_t x = __ballot(ms != 0u);
+        // the compare reads the extracted mask (a plain ballot of "bit set" has the compiler
+        // re-derive the bit from dg with a shift); 33 = ICMP_NE
+        const uint64_t x = __builtin_amdgcn_uicmp(ms, 0u, 33);
         // p & ~(x ^ m): LUT index (p << 2 | x << 1 | m) -> bits 4 and 7
         pl = __builtin_amdgcn_bitop3_b32(pl, (uint32_t)x, ms, 0x90);
         ph = __builtin_amdgcn_bitop3_b32(ph, (uint32_t)(x >> 32), ms, 0x90);
     }
     *peers_out = (uint32_t)__builtin_popcount(pl) + (uint32_t)__builtin_popcount(ph);
     return __builtin_amdgcn_mbcnt_hi(ph, __builtin_amdgcn_mbcnt_lo(pl, 0u));
+}
+
+template <int kBits>
+__device__ __forceinline__ uint32_t wave_match_rank(uint32_t dg, bool valid, uint32_t* peers_out) {
+    const uint64_t v = __ballot(valid);
+    return wave_match_rank_from<kBits>(dg, (uint32_t)v, (uint32_t)(v >> 32), peers_out);
+}
+
+// every lane takes part: all 64 lanes of the wave must be active at the call (full tiles)
+template <int kBits>
+__device__ __forceinline__ uint32_t wave_match_rank(uint32_t dg, uint32_t* peers_out) {
+    return wave_match_rank_from<kBits>(dg, 0xFFFFFFFFu, 0xFFFFFFFFu, peers_out);
 }
 
 // ParallelMemHash compat records' group key (compat.hip, chunked.hip): masked-ckey bits 1-30

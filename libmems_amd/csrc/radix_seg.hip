@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "mums_internal.h"
@@ -49,7 +50,8 @@ constexpr int kSortTile = MUMS_SORT_TILE;      // records per onesweep tile (lon
 #define MUMS_OS_NEXTHIST 0  // 1: pass p counts the pass-(p+1) digits (the histogram read covers digit 0 only)
 #endif
 #ifndef MUMS_OS_FUSED
-#define MUMS_OS_FUSED 0     // 1: fold lstart into the per-wave bases and the output offsets
+#define MUMS_OS_FUSED 1     // 1: fold lstart into the per-wave bases and the output offsets (one LDS
+                            // read per record in each scatter, and no digit kept per record: <= 80 VGPRs)
 #endif
 #ifndef MUMS_LOOKBACK
 #define MUMS_LOOKBACK 4
@@ -460,8 +462,11 @@ __device__ __forceinline__ void onesweep_load(const uint64_t* __restrict__ rin, 
 // its slot base into its ranks before the exchange), so a tile costs kT * 8 B + 4 KB of LDS.
 // kGath (the line sort's last pass): instead of record k, gout[o] = low 32 bits of
 // gsrc[low 32 bits of k] -- the permutation gather of the caller, done at the store
-template <int OB, int kIPT, bool kAlias = false, bool kLate = false, bool kGath = false>
-__global__ __launch_bounds__(OB) void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
+// kHi (the host sets it when shift >= 32): the pass's digit lies in the record's high word
+// Two blocks of the default shape (768 threads) per CU need six waves per SIMD, i.e. <= 80 VGPRs.
+template <int OB, int kIPT, bool kAlias = false, bool kLate = false, bool kGath = false, bool kHi = false>
+__global__ __launch_bounds__(OB) __attribute__((amdgpu_waves_per_eu(OB == 768 ? 6 : 1)))
+void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
                                                           uint64_t* __restrict__ rout,
                                                           const SegTile* __restrict__ tiles, uint32_t nclaims,
                                                           int shift, int pass, int npass,
@@ -487,6 +492,7 @@ __global__ __launch_bounds__(OB) void seg_onesweep_kernel(const uint64_t* __rest
     __shared__ uint32_t hcnt[kDigits];
     __shared__ uint32_t hnext[kDigits];   // next pass's digit counts (ghist_next != null)
     __shared__ uint4 s_desc;              // the claimed tile's descriptor (xd)
+    __shared__ uint32_t s_far;            // an output offset of this tile may pass 2^32 bytes
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 #if MUMS_OS_STATS
     unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -518,6 +524,7 @@ __global__ __launch_bounds__(OB) void seg_onesweep_kernel(const uint64_t* __rest
     }
     for (int i = tid; i < kW * kDigits; i += OB) (&wcnt[0][0])[i] = 0;
     if (tid < kDigits) { hcnt[tid] = 0; hnext[tid] = 0; }
+    if (tid == 0) s_far = 0;
     __syncthreads();
     const uint32_t c = __builtin_amdgcn_readfirstlane(s_tile);   // uniform: scalar descriptor loads
     if (xq ? c == 0xFFFFFFFFu : c >= nclaims) return;
@@ -540,62 +547,84 @@ __global__ __launch_bounds__(OB) void seg_onesweep_kernel(const uint64_t* __rest
     if (d.count == 0) return;
     OS_STAMP(1);
     const uint32_t q0 = wv * (kT / kW);
+    auto qof = [&](int r) -> uint32_t { return q0 + (uint32_t)r * 64u + (uint32_t)lane; };
+    // the pass's digit of a record: a 32-bit field of the high word when it lies there (kHi)
+    auto digit = [&](uint64_t k) -> uint32_t {
+        if constexpr (kHi) return ((uint32_t)(k >> 32) >> (shift - 32)) & 0xFFu;
+        else return (uint32_t)(k >> shift) & 0xFFu;
+    };
+    auto digit_next = [&](uint64_t k) -> uint32_t {
+        if constexpr (kHi) return ((uint32_t)(k >> 32) >> (shift - 24)) & 0xFFu;
+        else return (uint32_t)(k >> (shift + 8)) & 0xFFu;
+    };
+    // the bucket's first output record (the exclusive digit scan starts there): the stores
+    // address it plus a 32-bit byte offset when every offset of this tile fits
+    const uint32_t bb = __builtin_amdgcn_readfirstlane(dbase[((uint64_t)d.bucket * npass + pass) * kDigits]);
+    static_assert((uint64_t)kT * 8 < (1ull << 32), "32-bit byte offsets inside a tile");
+    // A tile holds kT records, except the last one of a bucket.  That one is padded with pad =
+    // kT - count all-ones keys: they have the highest digit and the highest positions, so the
+    // stable ranking puts them behind every record (LDS slots >= count, never stored) and the
+    // counts of digit 255 are pad too high, which its owner subtracts.  So no step between the
+    // loads and the stores has a per-record bounds predicate, and every lane of every wave
+    // takes part in the ranking; a uniform branch picks loads and stores without one for the
+    // full tiles.
+    const bool full = d.count == (uint32_t)kT;
+    const uint32_t pad = (uint32_t)kT - d.count;
     uint64_t key[kIPT];
     uint32_t rank[kIPT];
-    auto qof = [&](int r) -> uint32_t { return q0 + (uint32_t)r * 64u + (uint32_t)lane; };
-    #pragma unroll
-    for (int r = 0; r < kIPT; ++r) {
-        const uint32_t q = qof(r);
+    const char* tin = reinterpret_cast<const char*>(rin + d.start);   // uniform base + 32-bit offset
+    auto loads = [&](auto full_c) {
+        #pragma unroll
+        for (int r = 0; r < kIPT; ++r) {
+            const uint32_t q = qof(r);
+            const bool in = decltype(full_c)::value || q < d.count;
 #if MUMS_SORT_NT & 1
-        key[r] = q < d.count ? __builtin_nontemporal_load(rin + d.start + q) : 0ull;   // read once per pass
+            key[r] = in ? __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(tin + q * 8u)) : ~0ull;   // read once per pass
 #else
-        key[r] = q < d.count ? rin[d.start + q] : 0ull;
+            key[r] = in ? *reinterpret_cast<const uint64_t*>(tin + q * 8u) : ~0ull;
 #endif
-    }
+        }
+    };
+    if (full) loads(std::true_type{});
+    else loads(std::false_type{});
     if constexpr (!late) {
         // publish this tile's per-digit counts as soon as the keys are in: successors'
         // look-backs then rarely find an unpublished predecessor.  (Late: after the ranking,
         // from its per-wave counts -- for keys in runs of equal digits, whose per-record LDS
         // atomics here would serialise.)
         #pragma unroll
-        for (int r = 0; r < kIPT; ++r) {
-            const uint32_t q = qof(r);
-            if (q < d.count) atomicAdd(&hcnt[(uint32_t)(key[r] >> shift) & 0xFFu], 1u);
-        }
+        for (int r = 0; r < kIPT; ++r)
+            atomicAdd(&hcnt[digit(key[r])], 1u);
         __syncthreads();
         OS_STAMP(2);
         if (d.tb != 0 && tid < kDigits)
-            __hip_atomic_store(status + (uint64_t)t * kDigits + tid, kFlagAgg | hcnt[tid], __ATOMIC_RELAXED,
+            __hip_atomic_store(status + (uint64_t)t * kDigits + tid,
+                               kFlagAgg | (hcnt[tid] - (tid == kDigits - 1 ? pad : 0u)), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
     }
     if (ghist_next) {   // uniform: the next pass's histogram rides on this pass's read
         #pragma unroll
-        for (int r = 0; r < kIPT; ++r) {
-            const uint32_t q = qof(r);
-            if (q < d.count) atomicAdd(&hnext[(uint32_t)(key[r] >> (shift + 8)) & 0xFFu], 1u);
-        }
+        for (int r = 0; r < kIPT; ++r)
+            atomicAdd(&hnext[digit_next(key[r])], 1u);
     }
     #pragma unroll
     for (int r = 0; r < kIPT; ++r) {
-        const uint32_t q = qof(r);
-        const bool valid = q < d.count;
-        const uint32_t dg = (uint32_t)(key[r] >> shift) & 0xFFu;
         uint32_t tot;
-        const uint32_t rk = wave_match_rank<8>(dg, valid, &tot);
-        uint32_t old = 0;
-        if (valid) old = wcnt[wv][dg];
-        if (valid && rk == 0) wcnt[wv][dg] = old + tot;
+        const uint32_t rk = wave_match_rank<8>(digit(key[r]), &tot);
+        const uint32_t old = wcnt[wv][digit(key[r])];
+        if (rk == 0) wcnt[wv][digit(key[r])] = old + tot;
         rank[r] = old + rk;
     }
     __syncthreads();
     OS_STAMP(3);
     uint32_t v = 0, acc = 0;
     if (tid < kDigits) {
-        const int dg = tid;  // digit
+        const int dgt = tid;  // digit
         #pragma unroll
-        for (int w = 0; w < kW; ++w) { const uint32_t x = wcnt[w][dg]; wcnt[w][dg] = acc; acc += x; }
+        for (int w = 0; w < kW; ++w) { const uint32_t x = wcnt[w][dgt]; wcnt[w][dgt] = acc; acc += x; }
+        if (dgt == kDigits - 1) acc -= pad;
         // look back over the bucket's preceding tiles, then publish the inclusive prefix
-        uint32_t* st = status + (uint64_t)t * kDigits + dg;
+        uint32_t* st = status + (uint64_t)t * kDigits + dgt;
         if (late && d.tb != 0) __hip_atomic_store(st, kFlagAgg | acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         uint32_t prefix = 0;
         if (d.tb == 0) {
@@ -612,7 +641,7 @@ __global__ __launch_bounds__(OB) void seg_onesweep_kernel(const uint64_t* __rest
                 uint32_t sv[kLookback];
                 #pragma unroll
                 for (int k = 0; k < kLookback; ++k)
-                    sv[k] = (j - k >= tfirst) ? __hip_atomic_load(status + (uint64_t)(j - k) * kDigits + dg,
+                    sv[k] = (j - k >= tfirst) ? __hip_atomic_load(status + (uint64_t)(j - k) * kDigits + dgt,
                                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                               : kFlagInc;
                 int used = 0;
@@ -636,7 +665,10 @@ __global__ __launch_bounds__(OB) void seg_onesweep_kernel(const uint64_t* __rest
             __hip_atomic_store(st, kFlagInc | ((prefix + acc) & kValMask), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
         }
-        gofs[dg] = dbase[((uint64_t)d.bucket * npass + pass) * kDigits + dg] + prefix;
+        // output offset of the digit's run, relative to the bucket's start
+        const uint32_t rel = dbase[((uint64_t)d.bucket * npass + pass) * kDigits + dgt] - bb + prefix;
+        gofs[dgt] = rel;
+        if (rel >= (1u << 29) - (uint32_t)kT) s_far = 1u;   // a byte offset of this tile may pass 2^32
         // block-local digit starts
         v = acc;
         #pragma unroll
@@ -666,57 +698,64 @@ __global__ __launch_bounds__(OB) void seg_onesweep_kernel(const uint64_t* __rest
     if constexpr (kAlias) {   // slots first: the exchange overwrites the counts
         #pragma unroll
         for (int r = 0; r < kIPT; ++r) {
-            const uint32_t dg = (uint32_t)(key[r] >> shift) & 0xFFu;
 #if MUMS_OS_FUSED
-            rank[r] += wcnt[wv][dg];
+            rank[r] += wcnt[wv][digit(key[r])];
 #else
-            rank[r] += lstart[dg] + wcnt[wv][dg];
+            rank[r] += lstart[digit(key[r])] + wcnt[wv][digit(key[r])];
 #endif
         }
         __syncthreads();
         #pragma unroll
-        for (int r = 0; r < kIPT; ++r)
-            if (qof(r) < d.count) srec[rank[r]] = key[r];
+        for (int r = 0; r < kIPT; ++r) srec[rank[r]] = key[r];
     } else {
     #pragma unroll
     for (int r = 0; r < kIPT; ++r) {
-        const uint32_t q = qof(r);
-        if (q < d.count) {
-            const uint32_t dg = (uint32_t)(key[r] >> shift) & 0xFFu;
 #if MUMS_OS_FUSED
-            srec[wcnt[wv][dg] + rank[r]] = key[r];
+        srec[wcnt[wv][digit(key[r])] + rank[r]] = key[r];
 #else
-            srec[lstart[dg] + wcnt[wv][dg] + rank[r]] = key[r];
+        srec[lstart[digit(key[r])] + wcnt[wv][digit(key[r])] + rank[r]] = key[r];
 #endif
-        }
     }
     }
     __syncthreads();
     OS_STAMP(5);
-    #pragma unroll
-    for (int r = 0; r < kIPT; ++r) {
-        const uint32_t sidx = tid + r * OB;
-        if (sidx < d.count) {
-            const uint64_t k = srec[sidx];
-            const uint32_t dg = (uint32_t)(k >> shift) & 0xFFu;
+    uint64_t* bout = rout + bb;
+    uint32_t* bgout = kGath ? gout + bb : nullptr;
+    // far: some offset of this tile, in bytes, may not fit 32 bits (a bucket above 4 GB)
+    auto stores = [&](auto full_c, auto far_c) {
+        constexpr bool kFar = decltype(far_c)::value;
+        #pragma unroll
+        for (int r = 0; r < kIPT; ++r) {
+            const uint32_t sidx = tid + r * OB;
+            if (decltype(full_c)::value || sidx < d.count) {
+                const uint64_t k = srec[sidx];
+                const uint32_t sd = digit(k);
 #if MUMS_OS_FUSED
-            const uint64_t o = (uint64_t)(uint32_t)(gofs[dg] + sidx);   // gofs holds out offset - lstart (mod 2^32)
+                const uint32_t o = gofs[sd] + sidx;   // gofs holds out offset - lstart (mod 2^32)
 #else
-            const uint64_t o = (uint64_t)gofs[dg] + (sidx - lstart[dg]);
+                const uint32_t o = gofs[sd] + (sidx - lstart[sd]);
 #endif
-            if constexpr (kGath) {
-                gout[o] = (uint32_t)gsrc[(uint32_t)k];
-            } else {
+                if constexpr (kGath) {
+                    const uint32_t gv = (uint32_t)gsrc[(uint32_t)k];
+                    if constexpr (kFar) bgout[o] = gv;
+                    else *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(bgout) + o * 4u) = gv;
+                } else {
+                    uint64_t* op = kFar ? bout + o
+                                        : reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(bout) + o * 8u);
 #if MUMS_SORT_NT & 2
-                __builtin_nontemporal_store(k, rout + o);
+                    __builtin_nontemporal_store(k, op);
 #else
-                rout[o] = k;
+                    *op = k;
 #endif
+                }
             }
         }
-    }
+    };
+    if (s_far) stores(std::false_type{}, std::true_type{});
+    else if (full) stores(std::true_type{}, std::false_type{});
+    else stores(std::false_type{}, std::false_type{});
     if (ghist_next && tid < kDigits) {   // hnext complete: barriers since its atomics
-        const uint32_t c = hnext[tid];
+        const uint32_t c = hnext[tid] - (tid == kDigits - 1 ? pad : 0u);
         if (c) atomicAdd(&ghist_next[((uint64_t)d.bucket * npass + pass + 1) * kDigits + tid], c);
     }
 #if MUMS_OS_STATS
@@ -1488,9 +1527,14 @@ hipError_t seg_onesweep_sort(uint64_t* recA, uint64_t* recB, uint64_t n, int key
             uint32_t* sp = status + (uint64_t)p * ub * kDigits;
             const int sh = key_shift + 8 * p;
             uint32_t* tc = xq ? counters + 128 + 8 * p : counters + p;
-#define MUMS_OS_LAUNCH(OB, IPT, AL)                                                                               \
-    hipLaunchKernelGGL((seg_onesweep_kernel<OB, IPT, AL>), dim3((unsigned)ub), dim3(OB), 0, st, src, dst, otiles, \
-                       (uint32_t)ub, sh, p, npass, dbase, sp, tc, d_err, gn, xq, nullptr, nullptr, xd)
+#define MUMS_OS_LAUNCH1(OB, IPT, AL, HI)                                                                     \
+    hipLaunchKernelGGL((seg_onesweep_kernel<OB, IPT, AL, false, false, HI>), dim3((unsigned)ub), dim3(OB), 0, st, src, \
+                       dst, otiles, (uint32_t)ub, sh, p, npass, dbase, sp, tc, d_err, gn, xq, nullptr, nullptr, xd)
+#define MUMS_OS_LAUNCH(OB, IPT, AL)                     \
+    do {                                                \
+        if (sh >= 32) MUMS_OS_LAUNCH1(OB, IPT, AL, true); \
+        else MUMS_OS_LAUNCH1(OB, IPT, AL, false);       \
+    } while (0)
             if (key_runs && gout && p + 1 == npass) {   // the last pass stores gout[o] = gsrc[k]
                 hipLaunchKernelGGL((seg_onesweep_kernel<kSortBlock, kSortTile / kSortBlock, true, true, true>),
                                    dim3((unsigned)ub), dim3(kSortBlock), 0, st, src, dst, otiles, (uint32_t)ub, sh, p,
@@ -1512,6 +1556,7 @@ hipError_t seg_onesweep_sort(uint64_t* recA, uint64_t* recB, uint64_t n, int key
             default: MUMS_OS_LAUNCH(kSortBlock, kSortTile / kSortBlock, true); break;
             }
 #undef MUMS_OS_LAUNCH
+#undef MUMS_OS_LAUNCH1
         }
 #endif
         e = hipGetLastError();

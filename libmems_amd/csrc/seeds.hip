@@ -50,6 +50,39 @@ __device__ __forceinline__ uint32_t dna2(uint32_t c) {
     return one | (two << 1) | (three * 3u);
 }
 
+// The same table for the four bases of one dword of ASCII at once (SWAR): the code of byte j
+// comes out in bits 8j+1..8j.  ne(v, K): bit 7 of a byte is set iff the byte of v (< 0x80)
+// differs from K -- 0x7F + (v ^ K) carries into bit 7 exactly then, and never out of the byte.
+// *gap &= a word whose bytes have bit 7 clear where the input byte is '-'.
+__device__ __forceinline__ uint32_t dna2x4(uint32_t x, uint32_t* gap) {
+    constexpr uint32_t k01 = 0x01010101u, k7F = 0x7F7F7F7Fu, k80 = 0x80808080u;
+    auto ne = [&](uint32_t v, uint32_t K) -> uint32_t { return (v ^ (K * k01)) + k7F; };
+    const uint32_t lc = x | 0x20202020u;
+    const uint32_t l7 = lc & k7F;
+    const uint32_t n_bc = ne(lc & 0x7E7E7E7Eu, 'b');   // 'b' and 'c' differ in bit 0 only
+    const uint32_t n_y = ne(l7, 'y'), n_t = ne(l7, 't');
+    const uint32_t n_g = ne(l7, 'g'), n_s = ne(l7, 's'), n_k = ne(l7, 'k');
+    // bit 0 of the code: c b y t, bit 1: g s k t; bytes >= 0x80 (bit 7 of lc) are no letters
+    const uint32_t b0 = ~((n_bc & n_y & n_t) | lc) & k80;
+    const uint32_t b1 = ~((n_g & n_s & n_k & n_t) | lc) & k80;
+    *gap &= ne(x & k7F, '-') | x;
+    return (b0 >> 7) | (b1 >> 6);
+}
+
+// 16 bases (16 bytes of ASCII, the first in the lowest byte of v.x) -> one packed word, first
+// base in bits 31-30
+__device__ __forceinline__ uint32_t pack16(uint4 v, uint32_t* gap) {
+    const uint32_t in[4] = {v.x, v.y, v.z, v.w};
+    uint32_t f[4];
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t c = dna2x4(in[k], gap);   // codes at bits 0, 8, 16, 24
+        const uint32_t t = c | (c << 10);        // byte 2's code to bit 26 (byte 3's stays at 24)
+        f[k] = t | (t << 20);                    // byte 1's to 28, byte 0's to 30: the top byte
+    }
+    return (f[0] & 0xFF000000u) | ((f[1] >> 8) & 0x00FF0000u) | ((f[2] >> 16) & 0x0000FF00u) | (f[3] >> 24);
+}
+
 __device__ __forceinline__ int tile_genome(const GenomeTable& gt, uint32_t t) {
     int g = 0;
     for (int k = 1; k < gt.G; ++k) g += (t >= gt.tfirst[k]) ? 1 : 0;
@@ -61,7 +94,7 @@ __global__ __launch_bounds__(kBlock) void seed_pack_kernel(SeedSpec ss, GenomeTa
                                                            uint32_t* __restrict__ packed, K* __restrict__ ckey,
                                                            int msd_bits, uint32_t* __restrict__ hist, uint32_t T,
                                                            uint32_t* __restrict__ err, int swz) {
-    __shared__ uint8_t bytes[kTileBytes + 16];
+    __shared__ uint8_t bytes[kTileBytes + 16];   // the unaligned path's staging
     __shared__ uint32_t words[kTileWords];
     __shared__ uint32_t bh[1 << kMaxMsdBits];
     // XCD-grouped tiles (as the scatter below): the digit-major histogram columns hist[i * T + t]
@@ -79,10 +112,15 @@ __global__ __launch_bounds__(kBlock) void seed_pack_kernel(SeedSpec ss, GenomeTa
     const int nb = kMode == 1 ? (1 << msd_bits) : 0;
     for (int i = tid; i < nb; i += kBlock) bh[i] = 0;
 
-    // 1) stage the tile's ASCII in LDS (16-B loads when aligned)
+    // 1) + 2) 2-bit pack 16 bases per word (MSB first, as translate32); detect '-'.  Aligned:
+    // a thread packs the 16 bytes it loads (one 16-B load = one word; bytes past the genome
+    // are zero, which packs to zero and is no '-'), four bases per operation.  Otherwise the
+    // tile's ASCII is staged in LDS byte by byte and packed from there.
     const bool aligned = (((uintptr_t)(src + p0)) & 15) == 0;
+    uint32_t bad = 0;
     if (aligned) {
-        for (int c = tid; c * 16 < kTileBytes; c += kBlock) {
+        uint32_t gap = 0xFFFFFFFFu;
+        for (int c = tid; c < kTileWords; c += kBlock) {
             const uint64_t off = (uint64_t)c * 16;
             uint4 v = make_uint4(0, 0, 0, 0);
             if (off + 16 <= avail) {
@@ -93,25 +131,23 @@ __global__ __launch_bounds__(kBlock) void seed_pack_kernel(SeedSpec ss, GenomeTa
                     wv[k >> 2] |= (uint32_t)(uint8_t)src[p0 + off + k] << (8 * (k & 3));
                 v = make_uint4(wv[0], wv[1], wv[2], wv[3]);
             }
-            *reinterpret_cast<uint4*>(&bytes[off]) = v;
+            words[c] = pack16(v, &gap);
         }
+        bad = (~gap & 0x80808080u) != 0u;
     } else {
         for (int c = tid; c < kTileBytes; c += kBlock) bytes[c] = (uint64_t)c < avail ? (uint8_t)src[p0 + c] : 0;
-    }
-    __syncthreads();
-
-    // 2) 2-bit pack 16 bases per word (MSB first, as translate32); detect '-'
-    uint32_t bad = 0;
-    for (int wi = tid; wi < kTileWords; wi += kBlock) {
-        uint32_t word = 0;
-        #pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int b = wi * 16 + k;
-            const uint32_t c = b < kTileBytes ? bytes[b] : 0;
-            bad |= (c == '-') && ((uint64_t)b < avail);
-            word |= dna2(c) << (30 - 2 * k);
+        __syncthreads();
+        for (int wi = tid; wi < kTileWords; wi += kBlock) {
+            uint32_t word = 0;
+            #pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int b = wi * 16 + k;
+                const uint32_t c = b < kTileBytes ? bytes[b] : 0;
+                bad |= (c == '-') && ((uint64_t)b < avail);
+                word |= dna2(c) << (30 - 2 * k);
+            }
+            words[wi] = word;
         }
-        words[wi] = word;
     }
     if (bad) atomicOr(err, 1u);
     __syncthreads();
@@ -180,7 +216,9 @@ __global__ __launch_bounds__(kBlock) void seed_pack_kernel(SeedSpec ss, GenomeTa
 // kSide: the key has side_bits (<= 4) bits between the record's 64 - IB key bits and the
 // msd_bits MSD digit; they go to side[] at the record's position (msdsplit.hip splits the
 // buckets by them)
-template <int kMaxDig, uint64_t PAT = 0, int IB = 32, bool kChunk = false, int kSide = 0>
+// kRB: bits the ranking compares (the host passes the MSD width when it is a compile-time
+// constant below 8: msd_bits <= kRB)
+template <int kMaxDig, uint64_t PAT = 0, int IB = 32, bool kChunk = false, int kSide = 0, int kRB = 8>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void seed_scatter_kernel(SeedSpec ss, GenomeTable gt,
                                                               const uint32_t* __restrict__ packed, int msd_bits,
                                                               const uint32_t* __restrict__ hist, uint32_t T,
@@ -235,35 +273,58 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
 
     const uint64_t base = gt.base[g];
     const int q0 = wv * (kTile / kWaves);
+    // seed-mers of this tile; a tile is full (kTile of them) except a genome's last one
+    const uint32_t cnt_t = (m - p0) < (uint64_t)kTile ? (uint32_t)(m - p0) : (uint32_t)kTile;
+    // digits are < 2^msd_bits <= 2^kBits: the unused high bits rank as equal
+    constexpr int kBits = kMaxDig > 256 ? kMaxMsdBits : kRB;
     // the record's key part (<= 64 - IB <= 32 bits); its index part is base + p0 + q
     uint32_t r_key[kPerThread];
-    uint32_t r_pk[kPerThread];   // wave rank << 16 | digit; ~0 = not stored
-    #pragma unroll
-    for (int r = 0; r < kPerThread; ++r) {
-        const int q = q0 + r * 64 + lane;
-        const uint64_t p = p0 + (uint64_t)q;
-        bool valid = p < m;
-        const int wi = q >> 4, sh = 2 * (q & 15);
-        const uint64_t hi = ((uint64_t)words[wi] << 32) | words[wi + 1];
-        const uint64_t lo = words[wi + 2];
-        const uint64_t kv = ckey_of<PAT>((hi << sh) | ((lo << sh) >> 32), ss);
-        uint32_t d = valid ? (uint32_t)(kv >> klow) : 0u;
-        if (kChunk && !all_chunks) {
-            d -= dlo;
-            valid = valid && d < nbc;
-            d = valid ? d : 0u;
+    uint32_t r_pk[kPerThread];   // wave rank << 16 | digit; chunked: ~0 = not stored
+    // Unchunked, the positions behind the genome's last seed-mer take the highest digit: with
+    // the highest positions of the tile they rank behind every record (LDS slots >= cnt_t, never
+    // stored), and they inflate only that last digit's total, which no offset depends on.  So
+    // the ranking has no validity predicate and every lane takes part; kFull drops the bounds
+    // compare as well.
+    auto rank_tile = [&](auto full_c) {
+        #pragma unroll
+        for (int r = 0; r < kPerThread; ++r) {
+            const int q = q0 + r * 64 + lane;
+            const int wi = q >> 4, sh = 2 * (q & 15);
+            const uint64_t hi = ((uint64_t)words[wi] << 32) | words[wi + 1];
+            const uint64_t lo = words[wi + 2];
+            const uint64_t kv = ckey_of<PAT>((hi << sh) | ((lo << sh) >> 32), ss);
+            r_key[r] = (uint32_t)(kv & lmask);   // the record keeps the low 64 - IB bits
+            uint32_t tot;
+            if constexpr (kChunk) {
+                bool valid = (uint32_t)q < cnt_t;
+                uint32_t d = valid ? (uint32_t)(kv >> klow) : 0u;
+                if (!all_chunks) {
+                    d -= dlo;
+                    valid = valid && d < nbc;
+                    d = valid ? d : 0u;
+                }
+                const uint32_t rk = wave_match_rank<kBits>(d, valid, &tot);
+                uint32_t old = 0;
+                if (valid) old = wcnt[wv][d];
+                if (valid && rk == 0) wcnt[wv][d] = (uint16_t)(old + tot);
+                r_pk[r] = valid ? (((old + rk) << 16) | d) : 0xFFFFFFFFu;
+                if constexpr (kSide > 0)   // rank < 2^12: bits 28-31 are free (d < 256 here)
+                    if (valid) r_pk[r] |= ((uint32_t)(kv >> (64 - IB)) & ((1u << side_bits) - 1)) << 28;
+            } else {
+                uint32_t d = (uint32_t)(kv >> klow);
+                if constexpr (!decltype(full_c)::value) d = (uint32_t)q < cnt_t ? d : (uint32_t)(nd - 1);
+                const uint32_t rk = wave_match_rank<kBits>(d, &tot);
+                const uint32_t old = wcnt[wv][d];
+                if (rk == 0) wcnt[wv][d] = (uint16_t)(old + tot);
+                r_pk[r] = ((old + rk) << 16) | d;
+                if constexpr (kSide > 0)   // rank < 2^12: bits 28-31 are free (d < 256 here)
+                    r_pk[r] |= ((uint32_t)(kv >> (64 - IB)) & ((1u << side_bits) - 1)) << 28;
+            }
         }
-        r_key[r] = (uint32_t)(kv & lmask);   // the record keeps the low 64 - IB bits
-        uint32_t tot;
-        // digits are < 2^msd_bits <= kMaxDig: the unused high bits rank as equal
-        const uint32_t rk = wave_match_rank<(kMaxDig > 256 ? kMaxMsdBits : 8)>(d, valid, &tot);
-        uint32_t old = 0;
-        if (valid) old = wcnt[wv][d];
-        if (valid && rk == 0) wcnt[wv][d] = (uint16_t)(old + tot);
-        r_pk[r] = valid ? (((old + rk) << 16) | d) : 0xFFFFFFFFu;
-        if constexpr (kSide > 0)   // rank < 2^12: bits 28-31 are free (d < 256 here)
-            if (valid) r_pk[r] |= ((uint32_t)(kv >> (64 - IB)) & ((1u << side_bits) - 1)) << 28;
-    }
+    };
+    const bool full = !kChunk && cnt_t == (uint32_t)kTile;
+    if (full) rank_tile(std::true_type{});
+    else rank_tile(std::false_type{});
     __syncthreads();
     // per-digit wave offsets + block-local digit starts (each thread owns nd/256 digits)
     {
@@ -305,30 +366,38 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         }
     }
     __syncthreads();
+    const uint64_t idx0 = base + p0;   // global index of the tile's first seed-mer
     #pragma unroll
     for (int r = 0; r < kPerThread; ++r) {
         const uint32_t pk = r_pk[r];
-        if (pk != 0xFFFFFFFFu) {
+        if (!kChunk || pk != 0xFFFFFFFFu) {
             const uint32_t d = pk & 0xFFFFu;
             const uint32_t lp = (uint32_t)wcnt[wv][d] + ((pk >> 16) & (kSide > 0 ? 0xFFFu : 0xFFFFu));
-            srec[lp] = ((uint64_t)r_key[r] << IB) | (base + p0 + (uint64_t)(q0 + r * 64 + lane));
+            const uint32_t q = (uint32_t)(q0 + r * 64 + lane);
+            // 32 index bits hold every index of the contexts that use them: a 32-bit add
+            if constexpr (IB == 32) srec[lp] = ((uint64_t)r_key[r] << 32) | (uint32_t)((uint32_t)idx0 + q);
+            else srec[lp] = ((uint64_t)r_key[r] << IB) | (idx0 + (uint64_t)q);
             sdig[lp] = (DigT)(kSide > 0 ? (d | ((pk >> 28) << 8)) : d);   // + the side digit
         }
     }
     __syncthreads();
-    const uint64_t cnt = kChunk ? (uint64_t)s_kept : ((m - p0) < (uint64_t)kTile ? (m - p0) : (uint64_t)kTile);
-    #pragma unroll
-    for (int r = 0; r < kPerThread; ++r) {
-        const uint32_t s = tid + r * kBlock;
-        if (s < cnt) {
-            const uint32_t dd = sdig[s];
-            const uint32_t d = kSide > 0 ? (dd & 0xFFu) : dd;
-            const uint64_t b = (kChunk && all_chunks) ? cbase[d >> mb] : 0ull;
-            const uint64_t o = b + (uint64_t)(uint32_t)(gofs[d] + s);
-            rec[o] = srec[s];
-            if constexpr (kSide > 0) side[o] = (uint8_t)(dd >> 8);   // run order, like the records
+    const uint32_t cnt = kChunk ? s_kept : cnt_t;
+    auto stores = [&](auto full_c) {
+        #pragma unroll
+        for (int r = 0; r < kPerThread; ++r) {
+            const uint32_t s = tid + r * kBlock;
+            if (decltype(full_c)::value || s < cnt) {
+                const uint32_t dd = sdig[s];
+                const uint32_t d = kSide > 0 ? (dd & 0xFFu) : dd;
+                const uint64_t b = (kChunk && all_chunks) ? cbase[d >> mb] : 0ull;
+                const uint64_t o = b + (uint64_t)(uint32_t)(gofs[d] + s);
+                rec[o] = srec[s];
+                if constexpr (kSide > 0) side[o] = (uint8_t)(dd >> 8);   // run order, like the records
+            }
         }
-    }
+    };
+    if (full) stores(std::true_type{});
+    else stores(std::false_type{});
 }
 
 #pragma clang diagnostic pop
@@ -462,12 +531,20 @@ hipError_t launch_seed_scatter(const SeedSpec& ss, const GenomeTable& gt, const 
     }
     with_static_seed(ss.pattern, [&](auto pc) {
         constexpr uint64_t PAT = decltype(pc)::value;
-        if (msd_bits == 0)
+        if (msd_bits == 0) {
             hipLaunchKernelGGL(seed_scatter_flat_kernel<PAT>, dim3(ntiles), dim3(kBlock), 0, st, ss, gt, d_packed,
                                d_rec);
-        else
-            hipLaunchKernelGGL((seed_scatter_kernel<256, PAT>), dim3(ntiles), dim3(kBlock), 0, st, ss, gt, d_packed,
-                               msd_bits, d_hist_scanned, ntiles, d_rec);
+            return;
+        }
+        if constexpr (kStaticMsd<PAT> >= 1 && kStaticMsd<PAT> < 8) {
+            if (msd_bits == kStaticMsd<PAT>) {   // the default split: the ranking compares its bits only
+                hipLaunchKernelGGL((seed_scatter_kernel<256, PAT, 32, false, 0, kStaticMsd<PAT>>), dim3(ntiles),
+                                   dim3(kBlock), 0, st, ss, gt, d_packed, msd_bits, d_hist_scanned, ntiles, d_rec);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((seed_scatter_kernel<256, PAT>), dim3(ntiles), dim3(kBlock), 0, st, ss, gt, d_packed,
+                           msd_bits, d_hist_scanned, ntiles, d_rec);
     });
     return hipGetLastError();
 }
