@@ -197,15 +197,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kGl ? 6 
                                                                 DevCounters* __restrict__ ctr,
                                                                 double inv_table) {
     constexpr int kGRounds = kGSubRounds;   // this block's part of the tile
+    constexpr int kWaves = kBlock / 64;
     __shared__ uint64_t srec[kGSub];
     __shared__ uint16_t heads[kSubSlots];  // heads of groups of >= 2 records (<= kGSub / 2)
-    __shared__ uint32_t wcnt[kGRounds * (kBlock / 64)];
-    __shared__ uint32_t s_w[kBlock / 64];
+    __shared__ uint32_t wcnt[kGRounds * kWaves];
+    __shared__ uint32_t s_w[2][kWaves];    // accepted probes per wave, double-buffered over the probe loop
+    __shared__ uint32_t s_ng[kWaves];      // group heads per wave
     __shared__ uint32_t s_red[2];
     __shared__ uint64_t s_prev, s_next;
     __shared__ uint8_t s_gl[256];
     __shared__ uint32_t s_gb[kMaxG + 1];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: the wave's selects stay scalar
     const SegTile td = tiles[blockIdx.x / kGSplit];
     const uint32_t part0 = (blockIdx.x % kGSplit) * (uint32_t)kGSub;
     if (td.count <= part0) {
@@ -217,11 +220,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kGl ? 6 
     }
     const uint64_t tile0 = td.start + part0;
     const uint32_t cnt = td.count - part0 < (uint32_t)kGSub ? td.count - part0 : (uint32_t)kGSub;
-    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
 
     // 1) stage the tile (lane-contiguous, coalesced) + the records just before and after
     //    it.  The loads use clamped indices so all kGRounds are in flight before the
-    //    first LDS store.
+    //    first LDS store.  A lane keeps the masked keys of its records for the head detection.
+    uint32_t kx[kGRounds];
     {
         uint64_t x[kGRounds];
         #pragma unroll
@@ -233,6 +236,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kGl ? 6 
         for (int r = 0; r < kGRounds; ++r) {
             const uint32_t q = r * kBlock + threadIdx.x;
             if (q < cnt) srec[q] = x[r];
+            kx[r] = (uint32_t)(x[r] >> (IB + 1));   // (IB + 1 >= 33: the key has at most 31 bits)
         }
     }
     if (threadIdx.x == 0) s_prev = (tile0 > td.bstart) ? rec[tile0 - 1] : ~0ull;
@@ -248,28 +252,42 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kGl ? 6 
     __syncthreads();
 
     // 2) group heads in stream order; a head is kept only when its group has >= 2
-    //    records (a single record is never an AddHashEntry call)
-    uint32_t hmask = 0, ngrp = 0;
+    //    records (a single record is never an AddHashEntry call).  The lanes are
+    //    record-contiguous: the neighbours' keys come from the adjacent lanes (DPP wave
+    //    shifts), from LDS only at the two ends of a wave.
+    const bool first = tile0 == td.bstart;
+    const uint32_t kprev = (uint32_t)(s_prev >> (IB + 1)), knext = (uint32_t)(s_next >> (IB + 1));
+    uint32_t ke[kGRounds];   // lane 0: the key before the wave's first record; lane 63: after its last
+    #pragma unroll
+    for (int r = 0; r < kGRounds; ++r) ke[r] = 0;
+    if (lane == 0 || lane == 63) {
+        #pragma unroll
+        for (int r = 0; r < kGRounds; ++r) {
+            const uint32_t q = r * kBlock + threadIdx.x;
+            const uint32_t qe = lane == 0 ? q - 1 : q + 1;   // (q = 0: wraps, and takes kprev)
+            ke[r] = qe < cnt ? (uint32_t)(srec[qe] >> (IB + 1)) : (lane == 0 ? kprev : knext);
+        }
+    }
+    uint32_t hmask = 0, ngrp = 0;   // ngrp: uniform per wave
     #pragma unroll
     for (int r = 0; r < kGRounds; ++r) {
         const uint32_t q = r * kBlock + threadIdx.x;
-        bool keep = false;
-        if (q < cnt) {
-            const uint64_t here = srec[q] >> (IB + 1);
-            const uint64_t prev = (q == 0) ? ((tile0 == td.bstart) ? ~0ull : (s_prev >> (IB + 1)))
-                                           : (srec[q - 1] >> (IB + 1));
-            const uint64_t next = (q + 1 < cnt) ? (srec[q + 1] >> (IB + 1)) : (s_next >> (IB + 1));
-            const bool head = (q == 0 && tile0 == td.bstart) || here != prev;
-            ngrp += head ? 1u : 0u;
-            keep = head && next == here;
-        }
+        const uint32_t here = kx[r];
+        // wave_shr:1 / wave_shl:1: lane i reads lane i - 1 / i + 1; the end lane keeps ke[r]
+        const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp((int)ke[r], (int)here, 0x138, 0xf, 0xf, false);
+        uint32_t next = (uint32_t)__builtin_amdgcn_update_dpp((int)ke[r], (int)here, 0x130, 0xf, 0xf, false);
+        next = (q + 1 < cnt) ? next : knext;
+        const bool head = q < cnt && ((q == 0 && first) || here != prev);
+        const bool keep = head && next == here;
+        ngrp += (uint32_t)__popcll(__ballot(head));
         hmask |= (keep ? 1u : 0u) << r;
         const uint64_t bal = __ballot(keep);
-        if (lane == 0) wcnt[r * (kBlock / 64) + wv] = (uint32_t)__popcll(bal);
+        if (lane == 0) wcnt[r * kWaves + wv] = (uint32_t)__popcll(bal);
     }
+    if (lane == 0) s_ng[wv] = ngrp;
     __syncthreads();
     if (wv == 0) {   // exclusive scan of the kGRounds x waves counts (one wave, <= 64 entries)
-        constexpr int kE = kGRounds * (kBlock / 64);
+        constexpr int kE = kGRounds * kWaves;
         const uint32_t c0 = lane < kE ? wcnt[lane] : 0u;
         uint32_t inc = c0;
         #pragma unroll
@@ -285,17 +303,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kGl ? 6 
     for (int r = 0; r < kGRounds; ++r) {
         const bool keep = (hmask >> r) & 1u;
         const uint64_t bal = __ballot(keep);
-        if (keep) heads[wcnt[r * (kBlock / 64) + wv] + (uint32_t)__popcll(bal & lt)] = (uint16_t)(r * kBlock + threadIdx.x);
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        if (keep) heads[wcnt[r * kWaves + wv] + below] = (uint16_t)(r * kBlock + threadIdx.x);
     }
     __syncthreads();
     const uint32_t H = s_red[0];
 
-    // 3) one probe per lane, compacted in head order into this tile's slots
+    // 3) one probe per lane, compacted in head order into this tile's slots: the accepted
+    //    flags are scanned by ballot + mbcnt inside a wave and the waves' totals through LDS
+    //    (two buffers: one barrier per iteration)
     const TileRecViewT<IB> v{(lds_u64*)srec, rec, tile0, cnt};
     const bool fast = kFastOnly || (mp.repeat_tol == 0 && mp.enum_tol == 1);
+    const uint64_t want_mn = mp.masked ? mp.seq_mask : 0ull;   // uniform for the launch
     const double inv_t = inv_table;   // 1 / table_size from the host (a double division per block otherwise)
     const uint64_t sb = (uint64_t)blockIdx.x * kSubSlots;
-    uint32_t nrep = 0, base = 0;
+    uint32_t nrep = 0, base = 0, buf = 0;
     for (uint32_t c = 0; c < H; c += kBlock) {
         const uint32_t j = c + threadIdx.x;
         bool ok = false;
@@ -320,7 +342,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kGl ? 6 
                     for (int k = 0; k <= MG; ++k)
                         xb[k] = ((uint32_t)k <= (uint32_t)gt.G && h + k < td.bend) ? rec[h + k] : ~0ull;
                 }
-                ok = probe_fast_raw<MG, IB, use_gl>(xb, gt, mp, L, &off, &gsz, &glk);
+                ok = probe_fast_raw<MG, IB, use_gl>(xb, gt, want_mn, L, &off, &gsz, &glk);
                 if (gsz > (uint32_t)gt.G) {   // oversize group: rejected; count on for the report
                     uint64_t i = h + gsz;
                     const uint32_t k0 = (uint32_t)(xb[0] >> (IB + 1));
@@ -334,18 +356,30 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kGl ? 6 
             nrep += gsz > (uint32_t)kRepeatLimit;
             if (ok) bkt = bucket_of_fast(off, mp.table_size, inv_t);
         }
-        uint32_t tot;
-        const uint32_t o = blk_excl_scan(ok ? 1u : 0u, s_w, &tot);
+        const uint64_t bal = __ballot(ok);
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        if (lane == 0) s_w[buf][wv] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t pre = 0, tot = 0;
+        #pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            const uint32_t x = s_w[buf][w];
+            pre += (w < wv) ? x : 0u;
+            tot += x;
+        }
+        buf ^= 1u;
         if (ok) {
-            slot_info[sb + base + o] = h | ((uint64_t)(gsz > 65535u ? 65535u : gsz) << 32);
-            slot_bucket[sb + base + o] = bkt;
+            const uint32_t o = base + pre + below;
+            slot_info[sb + o] = h | ((uint64_t)(gsz > 65535u ? 65535u : gsz) << 32);
+            slot_bucket[sb + o] = bkt;
         }
         base += tot;
     }
     if (nrep) atomicAdd(&ctr->repeat_limit, (unsigned long long)nrep);   // rare (repeat-rich input only)
-    uint32_t gtot;
-    (void)blk_excl_scan(ngrp, s_w, &gtot);
     if (threadIdx.x == 0) {
+        uint32_t gtot = 0;   // (s_ng: written before the barriers of the head list)
+        #pragma unroll
+        for (int w = 0; w < kWaves; ++w) gtot += s_ng[w];
         tile_count[blockIdx.x] = base;
         tile_count[gridDim.x + 32 + blockIdx.x] = gtot;   // per-tile group count (summed by the host side)
     }

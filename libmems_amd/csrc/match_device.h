@@ -330,9 +330,44 @@ __device__ __forceinline__ void glook(const GLook& l, uint32_t idx, uint32_t* g,
     *b = ge ? b1 : b0;
 }
 
+// A record's genome and 1-based start in it (the decode shared by probe_fast_raw and
+// probe_row_fast): the LDS lookup, or one compare/select pass over the genome bases.
+template <int MG, int IB, bool kGl, typename IdxT>
+__device__ __forceinline__ void rec_genome_start(uint64_t x, const GenomeTable& gt, const GLook* glk, uint32_t* g_out,
+                                                 IdxT* s_out) {
+    const IdxT idx = (IdxT)(x & ((1ull << IB) - 1));
+    uint32_t g = 0;
+    IdxT b = 0;
+    if constexpr (kGl && IB == 32) {
+        uint32_t bb;
+        glook(*glk, (uint32_t)idx, &g, &bb);
+        b = bb;
+    } else {
+        const uint32_t G = (uint32_t)gt.G;
+        #pragma unroll
+        for (int j = 1; j < MG; ++j) {
+            const IdxT bj = (IdxT)gt.base[j];
+            const bool ge = (uint32_t)j < G && idx >= bj;
+            g = ge ? (uint32_t)j : g;
+            b = ge ? bj : b;
+        }
+    }
+    *g_out = g;
+    *s_out = idx - b + 1u;
+}
+
+// want_mn: MaskedMemHash's sequence mask when it selects (masked and seq_mask != 0), else 0 --
+// uniform for a launch, so the caller folds mp.masked / mp.seq_mask once.
+// The offset: with sr the reference's start (the smallest genome present), cnt members, the
+// members of the reference's parity forward and the others reversed,
+//   off = sum_fwd sv - sum_rev sv - cnt * sr - n_rev * L
+// (the reference's own term sv - sr is 0, so it needs no exclusion), from two sums that do not
+// depend on the reference: all members' starts, and those of parity 1.  Two's complement,
+// exact for every group the old per-record form accepted.  No genome twice <=> popcount(mask)
+// == cnt (an accepted group has cnt <= G <= MG members, all of them in the mask).
 template <int MG, int IB = 32, bool kGl = false>
-__device__ __forceinline__ bool probe_fast_raw(const uint64_t (&x)[MG + 1], const GenomeTable& gt,
-                                               const MatchParams& mp, int L, int64_t* offset, uint32_t* gsize,
+__device__ __forceinline__ bool probe_fast_raw(const uint64_t (&x)[MG + 1], const GenomeTable& gt, uint64_t want_mn,
+                                               int L, int64_t* offset, uint32_t* gsize,
                                                const GLook* glk = nullptr) {
     const uint32_t G = (uint32_t)gt.G;
     const uint32_t k0 = (uint32_t)(x[0] >> (IB + 1));
@@ -345,57 +380,39 @@ __device__ __forceinline__ bool probe_fast_raw(const uint64_t (&x)[MG + 1], cons
     }
     *gsize = cnt;
     MaskT<MG> mask = 0;
-    uint32_t gref = 64, pref = 0;
+    uint32_t gref = 64, pref = 0, n1 = 0;
     // 32-bit starts and bases for 32-bit record indices; 64-bit in the chunked mode
     using IdxT = typename std::conditional<(IB > 32), uint64_t, uint32_t>::type;
     IdxT sref = 0;
-    bool dup = false;
+    uint64_t tot = 0, sum1 = 0;   // the members' starts: all, parity 1 (<= MG terms below 2^IB)
     // record MG only bounds the run: an accepted probe has cnt <= G <= MG records, so it is
-    // never a member (cnt = MG + 1 is rejected below whatever mask, dup and off hold)
-    uint32_t gk[MG];
-    IdxT sk[MG];
+    // never a member (cnt = MG + 1 is rejected below whatever mask and off hold)
     #pragma unroll
     for (int k = 0; k < MG; ++k) {
-        const IdxT idx = (IdxT)(x[k] & ((1ull << IB) - 1));
-        uint32_t g = 0;
-        IdxT b = 0;
-        if constexpr (kGl && IB == 32) {
-            uint32_t bb;
-            glook(*glk, (uint32_t)idx, &g, &bb);
-            b = bb;
-        } else {
-            #pragma unroll
-            for (int j = 1; j < MG; ++j) {
-                const IdxT bj = (IdxT)gt.base[j];
-                const bool ge = (uint32_t)j < G && idx >= bj;
-                g = ge ? (uint32_t)j : g;
-                b = ge ? bj : b;
-            }
-        }
-        gk[k] = g;
-        sk[k] = idx - b + 1u;   // 1-based start in genome g
+        uint32_t g;
+        IdxT s;
+        rec_genome_start<MG, IB, kGl, IdxT>(x[k], gt, glk, &g, &s);
         const bool in = (uint32_t)k < cnt;
-        dup = dup || (in && ((mask >> g) & 1u));
+        const uint32_t par = (uint32_t)(x[k] >> IB) & 1u;
+        const IdxT d = in ? s : (IdxT)0;
+        const uint32_t pin = in ? par : 0u;
         mask |= in ? ((MaskT<MG>)1 << g) : (MaskT<MG>)0;
         const bool better = in && g < gref;
         gref = better ? g : gref;
-        sref = better ? sk[k] : sref;
-        pref = better ? (uint32_t)(x[k] >> IB) & 1u : pref;
+        sref = better ? s : sref;
+        pref = better ? par : pref;
+        tot += d;
+        sum1 += pin ? d : (IdxT)0;
+        n1 += pin;
     }
-    int64_t off = 0;
-    #pragma unroll
-    for (int k = 0; k < MG; ++k) {
-        const bool use = (uint32_t)k < cnt && gk[k] != gref;
-        const int64_t sv = (int64_t)sk[k], sr = (int64_t)sref;
-        const int64_t term = (((uint32_t)(x[k] >> IB) & 1u) != pref) ? (-sv - sr - (int64_t)L) : (sv - sr);
-        off += use ? term : 0;
-    }
-    *offset = off;
-    const bool accept = cnt >= 2 && cnt <= G && !dup;
-    if (mp.masked) {
-        const uint64_t match_number = match_number_of(mask, G);
-        return accept && (mp.seq_mask == 0 || match_number == mp.seq_mask);
-    }
+    const uint64_t dif = tot - 2 * sum1;                 // parity 0 minus parity 1
+    const uint32_t nrev = pref ? cnt - n1 : n1;
+    *offset = (int64_t)((pref ? 0 - dif : dif) - (uint64_t)cnt * (uint64_t)sref - (uint64_t)(nrev * (uint32_t)L));
+    uint32_t npres;
+    if constexpr (sizeof(MaskT<MG>) == 8) npres = (uint32_t)__popcll(mask);
+    else npres = (uint32_t)__popc(mask);
+    bool accept = cnt >= 2 && cnt <= G && npres == cnt;
+    if (want_mn) accept = accept && match_number_of(mask, G) == want_mn;
     return accept;
 }
 
@@ -407,30 +424,16 @@ template <int MG, int IB = 32, bool kGl = false>
 __device__ __forceinline__ void probe_row_fast(const uint64_t (&x)[MG], uint32_t cnt, const GenomeTable& gt, int L,
                                                Mhe<MG>& P, const GLook* glk = nullptr) {
     using IdxT = typename std::conditional<(IB > 32), uint64_t, uint32_t>::type;
-    const uint32_t G = (uint32_t)gt.G;
     int64_t st[MG];
     uint32_t gk[MG], pk[MG];
     #pragma unroll
     for (int k = 0; k < MG; ++k) {
-        const IdxT idx = (IdxT)(x[k] & ((1ull << IB) - 1));
-        uint32_t g = 0;
-        IdxT b = 0;
-        if constexpr (kGl && IB == 32) {
-            uint32_t bb;
-            glook(*glk, (uint32_t)idx, &g, &bb);
-            b = bb;
-        } else {
-            #pragma unroll
-            for (int j = 1; j < MG; ++j) {
-                const IdxT bj = (IdxT)gt.base[j];
-                const bool ge = (uint32_t)j < G && idx >= bj;
-                g = ge ? (uint32_t)j : g;
-                b = ge ? bj : b;
-            }
-        }
+        uint32_t g;
+        IdxT s;
+        rec_genome_start<MG, IB, kGl, IdxT>(x[k], gt, glk, &g, &s);
         gk[k] = (uint32_t)k < cnt ? g : 0xFFu;
         pk[k] = (uint32_t)(x[k] >> IB) & 1u;
-        st[k] = (int64_t)(idx - b) + 1;
+        st[k] = (int64_t)s;
     }
     uint32_t gref = 0xFFu, ref_par = 0;
     int64_t sref = 0;
