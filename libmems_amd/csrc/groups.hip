@@ -8,9 +8,10 @@
 // ((offset % T) + T) % T (MemHash.cpp:213).
 //
 // Here the merged stream is the radix-sorted record array; a group is a run of
-// equal ckey>>1.  One workgroup per 4096-record tile (probe_tile_rec_kernel for
-// the packed records: the tile is staged in LDS and the default-tolerance probe is
-// branch-free; probe_tile_kernel for the (key, index) pair path):
+// equal ckey>>1.  One workgroup per 4096-record tile of the (key, index) pair path
+// (probe_tile_kernel); two per 3968-record tile of the packed records, 1984 records each
+// (probe_tile_rec_kernel: the records are staged in LDS and the default-tolerance probe is
+// branch-free):
 //   1. lane-contiguous head detection (16 rounds), heads compacted into an LDS
 //      list in stream order (ballot + per-(round, wave) counts);
 //   2. every lane builds the probe of one head (no lane idles on non-heads);
@@ -31,12 +32,13 @@ namespace {
 constexpr int kGTile = kSegTile;
 constexpr int kGRounds = kGTile / kBlock;
 constexpr int kSlots = kGTile / 2;
-// packed-record probe stage: kGSplit workgroups per sort tile (half the LDS per block,
-// twice the blocks per CU to hide the record loads behind the other blocks' probe work)
-#ifndef MUMS_GROUP_SPLIT
-#define MUMS_GROUP_SPLIT 2
-#endif
-constexpr int kGSplit = MUMS_GROUP_SPLIT;
+// packed-record probe stage: kGSplit workgroups per group tile (half the LDS per block,
+// twice the blocks per CU to hide the record loads behind the other blocks' probe work).
+// kGSub and kGSubRounds are the LDS and round capacities of a workgroup; it takes kGTake
+// (<= kGSub) records, and the group tiles of the stream are kGSplit * kGTake = kProbeTile
+// records (mums_internal.h)
+constexpr int kGSplit = kProbeSplit;
+constexpr int kGTake = kProbeTake;
 constexpr int kGSub = kGTile / kGSplit;
 constexpr int kGSubRounds = kGSub / kBlock;
 constexpr int kSubSlots = kGSub / 2;
@@ -210,7 +212,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kGl ? 6 
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: the wave's selects stay scalar
     const SegTile td = tiles[blockIdx.x / kGSplit];
-    const uint32_t part0 = (blockIdx.x % kGSplit) * (uint32_t)kGSub;
+    const uint32_t part0 = (blockIdx.x % kGSplit) * (uint32_t)kGTake;   // (td.count <= kProbeTile)
     if (td.count <= part0) {
         if (threadIdx.x == 0) {
             tile_count[blockIdx.x] = 0;
@@ -219,7 +221,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kGl ? 6 
         return;
     }
     const uint64_t tile0 = td.start + part0;
-    const uint32_t cnt = td.count - part0 < (uint32_t)kGSub ? td.count - part0 : (uint32_t)kGSub;
+    const uint32_t cnt = td.count - part0 < (uint32_t)kGTake ? td.count - part0 : (uint32_t)kGTake;
 
     // 1) stage the tile (lane-contiguous, coalesced) + the records just before and after
     //    it.  The loads use clamped indices so all kGRounds are in flight before the
@@ -401,15 +403,15 @@ __global__ __launch_bounds__(kBlock) void probe_compact_kernel(const uint32_t* _
     }
 }
 
-__global__ void flat_tiles_kernel(uint64_t N, uint64_t nt, SegTile* __restrict__ tiles) {
+__global__ void flat_tiles_kernel(uint64_t N, uint64_t nt, uint32_t tile, SegTile* __restrict__ tiles) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt) return;
     SegTile d{};
-    d.start = t * kGTile;
+    d.start = t * tile;
     d.bstart = 0;
     d.bend = N;
     const uint64_t rem = N - d.start;
-    d.count = (uint32_t)(rem < (uint64_t)kGTile ? rem : (uint64_t)kGTile);
+    d.count = (uint32_t)(rem < (uint64_t)tile ? rem : (uint64_t)tile);
     d.hbase = 0;
     d.ntb = (uint32_t)nt;
     d.tb = (uint32_t)t;
@@ -832,10 +834,11 @@ hipError_t launch_gather_rows(const int64_t* src, const uint32_t* perm, uint64_t
     return hipGetLastError();
 }
 
-hipError_t launch_flat_tiles(uint64_t N, SegTile* d_tiles, hipStream_t st) {
-    const uint64_t nt = (N + kGTile - 1) / kGTile;
+hipError_t launch_flat_tiles(uint64_t N, SegTile* d_tiles, hipStream_t st, bool packed) {
+    const uint32_t tile = (uint32_t)(packed ? kProbeTile : kGTile);
+    const uint64_t nt = (N + tile - 1) / tile;
     if (nt == 0) return hipSuccess;
-    hipLaunchKernelGGL(flat_tiles_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, N, nt, d_tiles);
+    hipLaunchKernelGGL(flat_tiles_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, N, nt, tile, d_tiles);
     return hipGetLastError();
 }
 

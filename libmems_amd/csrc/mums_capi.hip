@@ -898,7 +898,7 @@ void records_live(mums_ctx* ctx) {
 
 int ensure_merge_space(mums_ctx* ctx, uint64_t n, int mb, int key_bits, ProbeSpace* ps) {
     records_live(ctx);
-    const uint64_t ub = seg_tiles_upper(n, mb);
+    const uint64_t ub = group_tiles_upper(n, mb);   // (>= the sort's seg_tiles_upper)
     HIPCHK(ctx->recA.ensure(n * 8 + 64));
     HIPCHK(ctx->recB.ensure(n * 8 + 64));
     HIPCHK(ctx->tiles.ensure(ub * sizeof(SegTile) + 64));
@@ -923,9 +923,10 @@ int merge_stage(mums_ctx* ctx, uint64_t n, int mb, int key_bits, const MatchPara
     if (!rB) rB = ctx->recB.as<uint64_t>();
     SegTile* tiles = ctx->tiles.as<SegTile>();
     const uint32_t* bstart = ctx->mstart.as<uint32_t>();
-    const uint64_t ub = seg_tiles_upper(n, mb);
+    const uint64_t ub = group_tiles_upper(n, mb);
     const bool prof = ctx->profiling;
-    HIPCHK(build_seg_tiles_from_starts(bstart, mb, n, tiles, &dc->ntiles, ctx->tmp.p, st));
+    // the group tiles of the probe stage (the onesweep sorts cut their own tiles)
+    HIPCHK(build_seg_tiles_from_starts(bstart, mb, n, tiles, &dc->ntiles, ctx->tmp.p, st, kProbeTile));
     int buf = 0;
     if (ib != 32 && !(n < (1ull << 30) && key_bits <= 32))
         return fail(ctx, MUMS_E_UNSUPPORTED, "33-bit records need < 2^30 records per merge");
@@ -943,8 +944,12 @@ int merge_stage(mums_ctx* ctx, uint64_t n, int mb, int key_bits, const MatchPara
         HIPCHK(seg_onesweep_sort(rA, rB, n, key_bits, mb, bstart, ctx->tmp.p, &dc->err, &buf, st,
                                  prof ? ctx->ev_ds : nullptr, ib, mask_parity));
         ctx->parity_masked = mask_parity && seg_onesweep_launches(key_bits) < (key_bits + 7) / 8;
-    } else
-        HIPCHK(seg_radix_sort(rA, rB, n, key_bits, tiles, ub, ctx->tmp.p, &buf, st, prof ? ctx->ev_ds : nullptr));
+    } else {   // the tile-wise sort takes kSegTile-record tiles in the same array
+        HIPCHK(build_seg_tiles_from_starts(bstart, mb, n, tiles, &dc->ntiles, ctx->tmp.p, st));
+        HIPCHK(seg_radix_sort(rA, rB, n, key_bits, tiles, seg_tiles_upper(n, mb), ctx->tmp.p, &buf, st,
+                              prof ? ctx->ev_ds : nullptr));
+        HIPCHK(build_seg_tiles_from_starts(bstart, mb, n, tiles, &dc->ntiles, ctx->tmp.p, st, kProbeTile));
+    }
     ctx->sorted_buf = buf;
     ctx->sorted_rec = buf ? rB : rA;
     ctx->sort_passes = wide ? seg_wide_passes(key_bits) : onesweep ? seg_onesweep_launches(key_bits) : (key_bits + 7) / 8;
@@ -1284,9 +1289,10 @@ int restart_stage(mums_ctx* ctx, const MatchParams& mp, const ProbeSpace& ps, hi
         ctx->sorted_buf ^= 1;
         ctx->sorted_rec = dst;
         SegTile* tiles = ctx->tiles.as<SegTile>();
-        HIPCHK(build_seg_tiles_from_starts(ctx->mstart.as<uint32_t>(), B, nl, tiles, &dc->ntiles, ctx->tmp.p, st));
+        HIPCHK(build_seg_tiles_from_starts(ctx->mstart.as<uint32_t>(), B, nl, tiles, &dc->ntiles, ctx->tmp.p, st,
+                                           kProbeTile));
         HIPCHK(hipMemsetAsync(&dc->repeat_limit, 0, 8, st));
-        rc = groups_dispatch<RecView>(ctx, RecView{dst}, tiles, seg_tiles_upper(nl, B), mp, ps.probe_info,
+        rc = groups_dispatch<RecView>(ctx, RecView{dst}, tiles, group_tiles_upper(nl, B), mp, ps.probe_info,
                                       ps.probe_bucket, ps.slot_info, ps.slot_bucket, st);
     } else {
         const size_t kb = ctx->key64 ? 8 : 4;
@@ -1677,7 +1683,7 @@ int run_pipeline_compat(mums_ctx* ctx, int stage) {
     HIPCHK(ctx->packed.ensure(words * 4 + 64));
     HIPCHK(ctx->counters.ensure(sizeof(DevCounters)));
     DevCounters* dc = ctx->counters.as<DevCounters>();
-    const uint64_t ntiles_groups = (N + kSegTile - 1) / kSegTile;
+    const uint64_t ntiles_groups = flat_group_tiles(N, true);   // (packed records: the smaller tiles)
     HIPCHK(ctx->ckey.ensure(N * 8 + 64));
     HIPCHK(ctx->kA.ensure(N * 8 + 64));
     HIPCHK(ctx->kB.ensure(N * 8 + 64));
@@ -2000,9 +2006,9 @@ int run_pipeline_compat(mums_ctx* ctx, int stage) {
         return MUMS_OK;
     }
     SegTile* tiles = ctx->tiles.as<SegTile>();
-    HIPCHK(launch_flat_tiles(n_live, tiles, st));
+    HIPCHK(launch_flat_tiles(n_live, tiles, st, ctx->compat_rec));
     if (ctx->compat_rec)
-        rc = groups_dispatch<RecView>(ctx, RecView{ctx->sorted_rec}, tiles, (n_live + kSegTile - 1) / kSegTile, mp,
+        rc = groups_dispatch<RecView>(ctx, RecView{ctx->sorted_rec}, tiles, flat_group_tiles(n_live, true), mp,
                                       ps.probe_info, ps.probe_bucket, ps.slot_info, ps.slot_bucket, st);
     else
         rc = groups_dispatch<PairView<uint64_t>>(
@@ -2190,8 +2196,8 @@ int mums_set_seed(mums_ctx* ctx, uint64_t pattern) {
 
 int mums_set_params(mums_ctx* ctx, uint32_t repeat_tol, uint32_t enum_tol, uint32_t table_size) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
-    if (table_size == 0 || table_size > 0x7FFFFFFFu)
-        return fail(ctx, MUMS_E_INVALID, "table size must be in [1, 2^31)");
+    if (table_size == 0 || table_size > 0x80000000u)
+        return fail(ctx, MUMS_E_INVALID, "table size must be in [1, 2^31]");
     ctx->repeat_tol = repeat_tol;
     ctx->enum_tol = enum_tol;
     ctx->table_size = table_size;
@@ -3122,8 +3128,9 @@ int shard_groups_chunked(mums_ctx* ctx, uint64_t* rec, const std::vector<uint32_
         for (uint32_t b = 0; b <= nbk; ++b) sub[b] = b < b0 ? 0u : (b < b1 ? bst[b] - (uint32_t)o : (uint32_t)nc);
         HIPCHK(hipMemcpyAsync(ctx->mstart.p, sub.data(), sub.size() * 4, hipMemcpyHostToDevice, st));
         SegTile* tiles = ctx->tiles.as<SegTile>();
-        HIPCHK(build_seg_tiles_from_starts(ctx->mstart.as<uint32_t>(), mb, nc, tiles, &dc->ntiles, ctx->tmp.p, st));
-        const uint64_t ub = seg_tiles_upper(nc, mb);
+        HIPCHK(build_seg_tiles_from_starts(ctx->mstart.as<uint32_t>(), mb, nc, tiles, &dc->ntiles, ctx->tmp.p, st,
+                                           kProbeTile));
+        const uint64_t ub = group_tiles_upper(nc, mb);
         int rc;
         if (ctx->rec_ib == 33)
             rc = groups_dispatch<RecViewT<33>>(ctx, RecViewT<33>{rec + o}, tiles, ub, mp, ps.probe_info,
@@ -3225,7 +3232,7 @@ int shard_chunk_rows(mums_ctx* ctx, hipStream_t st) {
     if (!shard_rows_from_all(ctx) || ctx->shard_rows_built) return MUMS_OK;
     if (ctx->enum_tol > 1 || ctx->pairwise) return shard_enum_rows(ctx, st);
     ProbeSpace ps{};
-    int rc = ensure_probe_space(ctx, ctx->shard_n, seg_tiles_upper(ctx->shard_n, ctx->shard_mb), &ps);
+    int rc = ensure_probe_space(ctx, ctx->shard_n, group_tiles_upper(ctx->shard_n, ctx->shard_mb), &ps);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(ctx->counters.p, 0, sizeof(DevCounters), st));
     rc = shard_groups_chunked(ctx, const_cast<uint64_t*>(ctx->sorted_rec), ctx->shard_bst, ps, true, st);
@@ -3267,10 +3274,11 @@ int shard_regroup(mums_ctx* ctx, uint64_t* dst, uint64_t nl, const std::vector<u
     ctx->live_n = nl;
     ctx->live_bst = bst;
     SegTile* tiles = ctx->tiles.as<SegTile>();
-    HIPCHK(build_seg_tiles_from_starts(ctx->mstart.as<uint32_t>(), mb, nl, tiles, &dc->ntiles, ctx->tmp.p, st));
+    HIPCHK(build_seg_tiles_from_starts(ctx->mstart.as<uint32_t>(), mb, nl, tiles, &dc->ntiles, ctx->tmp.p, st,
+                                       kProbeTile));
     HIPCHK(hipMemsetAsync(&dc->repeat_limit, 0, 8, st));
     const MatchParams mp{ctx->repeat_tol, ctx->enum_tol, ctx->table_size, ctx->masked, ctx->seq_mask};
-    const uint64_t ub = seg_tiles_upper(nl, mb);
+    const uint64_t ub = group_tiles_upper(nl, mb);
     int rc;
     if (ctx->rec_ib == 33)
         rc = groups_dispatch<RecViewT<33>>(ctx, RecViewT<33>{dst}, tiles, ub, mp, ps.probe_info, ps.probe_bucket,
@@ -5217,8 +5225,8 @@ int run_pipeline_chunked(mums_ctx* ctx, int stage) {
             if (rc) return rc;
         }
         SegTile* tiles = ctx->tiles.as<SegTile>();
-        const uint64_t ub = seg_tiles_upper(n_c, mb);
-        HIPCHK(build_seg_tiles_from_starts(bstart, mb, n_c, tiles, &dc->ntiles, ctx->tmp.p, st));
+        const uint64_t ub = group_tiles_upper(n_c, mb);
+        HIPCHK(build_seg_tiles_from_starts(bstart, mb, n_c, tiles, &dc->ntiles, ctx->tmp.p, st, kProbeTile));
         if (!resident) {
             int buf = 0;
             HIPCHK(seg_onesweep_sort(rA, rB, n_c, 31, mb, bstart, ctx->tmp.p, &dc->err, &buf, st,

@@ -38,6 +38,24 @@ constexpr int kSeedTile = MUMS_SEED_TILE;  // positions per key-kernel workgroup
 #define MUMS_SEG_TILE 4096
 #endif
 constexpr int kSegTile = MUMS_SEG_TILE; // records per sort / group tile
+// Packed-record probe stage (groups.hip): kProbeSplit workgroups per group tile, each taking
+// kProbeTake records.  A workgroup stages up to kSegTile / kProbeSplit records and probes
+// kBlock group heads per round of its loop; it takes a little less than it could stage, so that
+// at 8 genomes the heads of the groups of >= 2 records (one per ~7.96 records) fit one round:
+// 2048 records hold 257.4 +- 2.1 of them, 1984 hold 249.4 with a maximum of 256.
+// The group tiles of the packed-record stream are therefore kProbeTile records, cut per MSD
+// bucket like the sort's.
+#ifndef MUMS_GROUP_SPLIT
+#define MUMS_GROUP_SPLIT 2
+#endif
+#ifndef MUMS_PROBE_TAKE
+#define MUMS_PROBE_TAKE 1984
+#endif
+constexpr int kProbeSplit = MUMS_GROUP_SPLIT;
+constexpr int kProbeTake = MUMS_PROBE_TAKE;
+constexpr int kProbeTile = kProbeSplit * kProbeTake;
+static_assert(kSegTile % kProbeSplit == 0 && kProbeTake >= 2 && kProbeTake <= kSegTile / kProbeSplit,
+              "a probe workgroup takes at most what it stages");
 constexpr int kLocalIPT = 16;        // records per lane of the LDS-resident local sort (local_sort.hip)
 constexpr int kMaxMsdBits = 11;      // packed path: 2w+1 <= 32 + 11
 constexpr int kMaxSegBucketBits = 12; // segmented sorts: buckets of a merge (sharded 33-bit records at w21: 12 MSD bits)
@@ -288,6 +306,9 @@ hipError_t seg_onesweep_sort_wide(uint64_t* recA, uint64_t* recB, uint64_t n, in
                                   hipStream_t st, hipEvent_t* ev_ds, int key_shift = 32);
 
 // groups.hip
+// group tiles of a stream of n records in 2^msd_bits buckets: kProbeTile records each for
+// packed records (upper bound, as seg_tiles_upper), kSegTile-record flat tiles for the pair path
+inline uint64_t group_tiles_upper(uint64_t n, int msd_bits) { return seg_tiles_upper(n, msd_bits, kProbeTile); }
 uint64_t group_slot_count(uint64_t ntiles);
 // probe-stage workgroups (= tile_count entries) for ntiles tiles (packed records: split tiles)
 uint64_t group_blocks(uint64_t ntiles, bool packed);
@@ -344,8 +365,12 @@ hipError_t launch_dest_first(const uint32_t* sdest, uint64_t P, uint32_t* first,
 hipError_t launch_entry_first(const uint32_t* scdest, uint64_t nch, const uint32_t* rcount, const uint32_t* perm,
                               const uint32_t* sdest, uint64_t K, const uint32_t* chain_of, const uint32_t* cinv,
                               const uint32_t* rstart, uint32_t* efirst, hipStream_t st);
-// flat tiles over [0, N) for the pair path (one bucket)
-hipError_t launch_flat_tiles(uint64_t N, SegTile* d_tiles, hipStream_t st);
+// one bucket [0, N) cut into group tiles: kProbeTile records for packed records, else kSegTile
+hipError_t launch_flat_tiles(uint64_t N, SegTile* d_tiles, hipStream_t st, bool packed = false);
+inline uint64_t flat_group_tiles(uint64_t N, bool packed) {
+    const uint64_t tile = packed ? kProbeTile : kSegTile;
+    return (N + tile - 1) / tile;
+}
 
 // replay.hip
 hipError_t launch_bucket_ranges(const uint32_t* sb, uint64_t P, uint32_t* bstart, uint32_t* bend, uint32_t* d_max,

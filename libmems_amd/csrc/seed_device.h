@@ -121,6 +121,77 @@ __device__ __forceinline__ uint32_t ckey_top_static(uint64_t mer) {
     return ft < rt ? ft : rt;
 }
 
+// The same digit from two 32-bit fields instead of the 64-bit window: top_K(v) needs only the
+// pattern positions under the first B = ceil(K/2) care bases (the head), top_K(rc) only those
+// under the last B (the tail).  head = the 16 bases from the window's first base on, tail = the
+// 16 bases from pattern position toff on (the position of the B-th care base from the end), each
+// with its first base in bits 31-30.  Usable when both spans fit 16 bases (kTopFields).
+struct TopRuns {
+    int nh = 0, nt = 0, hspan = 0, tspan = 0, toff = 0;
+    int hsh[16] = {}, tsh[16] = {};   // right shift (left when negative) of the field, per run
+    uint32_t hmask[16] = {}, tmask[16] = {};
+};
+
+constexpr TopRuns top_runs(uint64_t pat, int B) {
+    TopRuns T{};
+    const SeedRuns R = seed_runs(pat);
+    if (B < 1 || B > 16 || B > R.w) return T;
+    // (pattern position k = bit L - 1 - k of pat, as seed_runs)
+    // head: the c-th care base (pattern position k) -> bits 2(B-1-c)+1 .. 2(B-1-c)
+    int c = 0;
+    for (int k = 0; k < R.L && c < B; ++k) {
+        if (!((pat >> (R.L - 1 - k)) & 1)) continue;
+        T.hspan = k + 1;
+        if (k < 16) {
+            const int dst = 2 * (B - 1 - c), sh = (30 - 2 * k) - dst;
+            if (T.nh > 0 && T.hsh[T.nh - 1] == sh) T.hmask[T.nh - 1] |= 3u << dst;
+            else { T.hsh[T.nh] = sh; T.hmask[T.nh] = 3u << dst; ++T.nh; }
+        }
+        ++c;
+    }
+    // tail: the c-th care base from the end -> bits 2c+1 .. 2c
+    c = 0;
+    for (int k = R.L - 1; k >= 0 && c < B; --k) {
+        if (!((pat >> (R.L - 1 - k)) & 1)) continue;
+        T.toff = k;
+        ++c;
+    }
+    T.tspan = R.L - T.toff;
+    c = 0;
+    for (int k = R.L - 1; k >= 0 && c < B; --k) {
+        if (!((pat >> (R.L - 1 - k)) & 1)) continue;
+        if (k - T.toff < 16) {
+            const int dst = 2 * c, sh = (30 - 2 * (k - T.toff)) - dst;
+            if (T.nt > 0 && T.tsh[T.nt - 1] == sh) T.tmask[T.nt - 1] |= 3u << dst;
+            else { T.tsh[T.nt] = sh; T.tmask[T.nt] = 3u << dst; ++T.nt; }
+        }
+        ++c;
+    }
+    return T;
+}
+
+template <uint64_t PAT, int K>
+constexpr bool kTopFields = PAT != 0 && top_runs(PAT, (K + 1) / 2).nh > 0 && top_runs(PAT, (K + 1) / 2).hspan <= 16 &&
+                            top_runs(PAT, (K + 1) / 2).tspan <= 16;
+
+template <uint64_t PAT, int K>
+__device__ __forceinline__ uint32_t ckey_top_fields(uint32_t head, uint32_t tail) {
+    constexpr int B = (K + 1) / 2;
+    constexpr TopRuns T = top_runs(PAT, B);
+    static_assert(kTopFields<PAT, K>, "head or tail wider than one field");
+    uint32_t hv = 0, tv = 0;   // the top and the low 2B bits of v
+    #pragma unroll
+    for (int r = 0; r < T.nh; ++r) hv |= (T.hsh[r] >= 0 ? (head >> T.hsh[r]) : (head << -T.hsh[r])) & T.hmask[r];
+    #pragma unroll
+    for (int r = 0; r < T.nt; ++r) tv |= (T.tsh[r] >= 0 ? (tail >> T.tsh[r]) : (tail << -T.tsh[r])) & T.tmask[r];
+    const uint32_t ft = hv >> (2 * B - K);
+    const uint32_t lowc = ~tv & (uint32_t)((1ull << (2 * B)) - 1);
+    uint32_t rr = __builtin_bitreverse32(lowc) >> (32 - 2 * B);
+    rr = ((rr >> 1) & 0x55555555u) | ((rr & 0x55555555u) << 1);
+    const uint32_t rt = rr >> (2 * B - K);
+    return ft < rt ? ft : rt;
+}
+
 // the patterns with compiled-in run tables (getSeed(15), getSeed(19): SeedMasks.h)
 constexpr uint64_t kSeedW15 = 0x7ac9afull;
 constexpr uint64_t kSeedW19 = 0x7b974efull;

@@ -169,6 +169,27 @@ __global__ __launch_bounds__(kBlock) void seed_pack_kernel(SeedSpec ss, GenomeTa
         // 8 bits first (msdsplit.hip)
         constexpr int kTop = kStaticMsd<PAT> > 8 ? 8 : kStaticMsd<PAT>;
         if (msd_bits == kTop) {
+            if constexpr (kTopFields<PAT, kTop> && seed_runs(PAT).L <= kHalo + 1 && kPerThread == 16) {
+                // a lane takes the 16 positions of one packed word: the word and its two successors
+                // are loaded once, and the head and tail fields of a position are one funnel shift
+                // each (a histogram needs no position order).  The tail field of position j starts
+                // at base j + toff of the three words; its bases past word 2 (L <= 33: none under
+                // the tail's care bases) read as zero.
+                constexpr int kToff = top_runs(PAT, (kTop + 1) / 2).toff;
+                const uint32_t w[4] = {words[tid], words[tid + 1], words[tid + 2], 0u};
+                const uint64_t q0 = p0 + (uint64_t)tid * 16;
+                const int rem = q0 >= m ? 0 : (m - q0 < 16 ? (int)(m - q0) : 16);
+                #pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const int a = (j + kToff) >> 4, s = (j + kToff) & 15;   // constants once unrolled
+                    const uint32_t head = j == 0 ? w[0] : __builtin_amdgcn_alignbit(w[0], w[1], 32 - 2 * j);
+                    const uint32_t tail = s == 0 ? w[a] : __builtin_amdgcn_alignbit(w[a], w[a + 1], 32 - 2 * s);
+                    if (j < rem) atomicAdd(&bh[ckey_top_fields<PAT, kTop>(head, tail)], 1u);
+                }
+                __syncthreads();
+                for (int i = tid; i < nb; i += kBlock) hist[(uint64_t)i * T + t] = bh[i];
+                return;
+            }
             #pragma unroll 4
             for (int j = 0; j < kPerThread; ++j) {
                 const int q = tid + j * kBlock;
