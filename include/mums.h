@@ -221,6 +221,17 @@ int  mums_progress_log_copy(mums_ctx* ctx, char* text, uint64_t capacity, uint64
  * append the cut-off overlaps without that genome (multiplicity > 1).  Same result and
  * order as the reference on the same MatchList. */
 int  mums_eliminate_overlaps(mums_ctx* ctx);
+/* EliminateOverlaps_v2 (libMems/ProgressiveAligner.h:300-406, progressiveMauve's version:
+ * ProgressiveAligner.cpp:646-659 pairwiseAnchorSearch, :961, :965, :2018, :2114, :3407, :3593)
+ * on the context's MatchList, in place.  Per id of seq_ids, in the given order (ids may
+ * repeat): the same std::sort as above, then the smaller of every overlapping pair is cropped
+ * (CropLeft / CropRight by the orientation in that sequence) or deleted; with eliminate_both,
+ * both matches of a pair that is not checkConsistent (:272-291).  processNewMatch (:260-271)
+ * never keeps a cut-off overlap of a Match (its Length(seqI) is 0 once Start(seqI) is
+ * NO_MATCH), so the list only shrinks.
+ * seq_ids == NULL: every sequence in order (the two-argument overload, :397-406); a non-NULL
+ * seq_ids with count == 0 does nothing; an id >= the sequence count is MUMS_E_INVALID. */
+int  mums_eliminate_overlaps_v2(mums_ctx* ctx, const uint32_t* seq_ids, uint32_t count, int eliminate_both);
 /* The caller's MatchList (count x seq_count signed starts, NO_MATCH = 0, lengths) becomes
  * the context's result, for mums_eliminate_overlaps / the filters on lists that did not
  * come from this context's FindMatches (Aligner.cpp:920 gap_list, :1580 mlist). */

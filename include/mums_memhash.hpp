@@ -376,6 +376,17 @@ public:
     }
     // EliminateOverlaps (Aligner.cpp:62-176) of the last MatchList, on the device
     void EliminateOverlaps() { check(mums_eliminate_overlaps(ctx_)); }
+    // EliminateOverlaps_v2 (ProgressiveAligner.h:300-406, progressiveMauve's version) of the last
+    // MatchList, on the device: every sequence in order (the overload at :397-406) ...
+    void EliminateOverlaps_v2(bool eliminate_both = false) {
+        check(mums_eliminate_overlaps_v2(ctx_, nullptr, 0, eliminate_both));
+    }
+    // ... or the sequences of seq_ids, in that order (:301); an empty list does nothing
+    void EliminateOverlaps_v2(const std::vector<uint32_t>& seq_ids, bool eliminate_both = false) {
+        static const uint32_t none = 0;   // an empty vector's data() may be null, which means "all"
+        check(mums_eliminate_overlaps_v2(ctx_, seq_ids.empty() ? &none : seq_ids.data(), (uint32_t)seq_ids.size(),
+                                         eliminate_both));
+    }
     // a caller's MatchList (M x G starts + lengths) as the current result, e.g. to run
     // EliminateOverlaps / the filters on a list the caller assembled
     void LoadMatches(const std::vector<uint64_t>& lengths, const std::vector<int64_t>& starts, uint32_t G) {

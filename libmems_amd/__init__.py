@@ -110,7 +110,7 @@ EXPORTED_SYMBOLS = [
     "mums_shard_restart_info", "mums_shard_tie_flags", "mums_shard_tie_replay", "mums_shard_tie_apply",
     "mums_genome_device", "mums_shard_chain_label", "mums_shard_chain_export", "mums_shard_find_labelled",
     "mums_shard_chain_info", "mums_shard_chain_entries", "mums_shard_entry_thresholds", "mums_shard_kept_export",
-    "mums_shard_find_kept", "mums_comm_exchange_info",
+    "mums_shard_find_kept", "mums_comm_exchange_info", "mums_eliminate_overlaps_v2",
 ]
 
 # mums_comm_ops (include/mums.h): the caller's transport as two host callbacks
@@ -200,6 +200,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mums_mem_table_count.argtypes = [vp, vp, u32]
     lib.mums_get_offset_log.argtypes = [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u32)]
     lib.mums_eliminate_overlaps.argtypes = [vp]
+    lib.mums_eliminate_overlaps_v2.argtypes = [vp, vp, u32, ctypes.c_int]
     lib.mums_load_matches.argtypes = [vp, u32, u64, vp, vp]
     lib.mums_debug_std_sort.argtypes = [vp, vp, u64, ctypes.c_int, vp]
     lib.mums_comm_unique_id.argtypes = [vp, u64]
@@ -563,6 +564,23 @@ class MemHash:
         """EliminateOverlaps (Aligner.cpp:62-176) of the current MatchList, on the GPU."""
         self._check(self._lib.mums_eliminate_overlaps(self._ctx))
 
+    def EliminateOverlaps_v2(self, seq_ids=None, eliminate_both: bool = False) -> None:
+        """EliminateOverlaps_v2 (ProgressiveAligner.h:300-406, progressiveMauve's version) of the
+        current MatchList, on the GPU.  seq_ids: the sequences whose overlaps are eliminated, in
+        that order (may repeat); None = every sequence (the two-argument overload, :397-406).
+        eliminate_both: crop / delete both matches of a pair that is not checkConsistent
+        (:272-291).  The list only shrinks: processNewMatch (:260-271) keeps no copy of a Match."""
+        if seq_ids is None:
+            self._check(self._lib.mums_eliminate_overlaps_v2(self._ctx, None, 0, int(bool(eliminate_both))))
+            return
+        for i in seq_ids:
+            if not 0 <= int(i) < 2 ** 32:
+                raise MumsError(MUMS_E_INVALID, f"EliminateOverlaps_v2: sequence id {i} out of range")
+        n = len(seq_ids)
+        ids = np.zeros(max(n, 1), dtype=np.uint32)   # an empty list is still a non-NULL pointer: no pass
+        ids[:n] = [int(i) for i in seq_ids]
+        self._check(self._lib.mums_eliminate_overlaps_v2(self._ctx, ids.ctypes.data, n, int(bool(eliminate_both))))
+
     def LoadMatches(self, ml: "MatchList") -> None:
         """Make a MatchList (e.g. one the caller edited) this object's current result."""
         lengths = np.ascontiguousarray(ml.lengths, dtype=np.uint64)
@@ -812,6 +830,14 @@ def EliminateOverlaps(ml: "MatchList", device: int = 0) -> "MatchList":
         return mh.GetMatchList()
 
 
+def EliminateOverlaps_v2(ml: "MatchList", seq_ids=None, eliminate_both: bool = False, device: int = 0) -> "MatchList":
+    """EliminateOverlaps_v2 (ProgressiveAligner.h:300) of a MatchList on the GPU; returns the new list."""
+    with MemHash(device) as mh:
+        mh.LoadMatches(ml)
+        mh.EliminateOverlaps_v2(seq_ids, eliminate_both)
+        return mh.GetMatchList()
+
+
 class MaskedMemHash(MemHash):
     """MaskedMemHash (MaskedMemHash.h:25-40): hash only seeds whose genome-presence bitmap equals the mask."""
 
@@ -847,5 +873,5 @@ class PairwiseMatchFinder(MemHash):
 __all__ = [
     "MemHash", "MaskedMemHash", "ParallelMemHash", "PairwiseMatchFinder", "MatchList", "MumsError", "GapInSequence", "getSeed", "getSeedLength",
     "getSeedWeight", "getDefaultSeedWeight", "load_library", "EXPORTED_SYMBOLS", "STAGE_SEEDS", "STAGE_ALL", "ShardedMemHash",
-    "shard_key_ranges", "EliminateOverlaps",
+    "shard_key_ranges", "EliminateOverlaps", "EliminateOverlaps_v2",
 ]

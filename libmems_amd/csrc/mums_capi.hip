@@ -2938,6 +2938,35 @@ int mums_eliminate_overlaps(mums_ctx* ctx) {
     return MUMS_OK;
 }
 
+// EliminateOverlaps_v2 (ProgressiveAligner.h:300-406) on the context's MatchList, in place
+int mums_eliminate_overlaps_v2(mums_ctx* ctx, const uint32_t* seq_ids, uint32_t count, int eliminate_both) {
+    if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (ctx->stage_done < MUMS_STAGE_ALL) return fail(ctx, MUMS_E_INVALID, "no completed FindMatches on this context");
+    if (ctx->M >= 0xFFFFFFF0ull) return fail(ctx, MUMS_E_UNSUPPORTED, "EliminateOverlaps_v2 of more than 2^32 matches");
+    const int G = ctx->gt.G;
+    std::vector<uint32_t> ids;
+    if (seq_ids) {
+        ids.assign(seq_ids, seq_ids + count);
+        for (uint32_t id : ids)
+            if (id >= (uint32_t)G) return fail(ctx, MUMS_E_INVALID, "EliminateOverlaps_v2: sequence id out of range");
+        if (ids.empty()) return MUMS_OK;   // no pass: the list stays as it is
+    } else {   // the two-argument overload (:397-406): every sequence in order
+        ids.resize((size_t)G);
+        for (int g = 0; g < G; ++g) ids[g] = (uint32_t)g;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    uint64_t n = 0;
+    HIPCHK(eliminate_overlaps_v2_device(ctx->eo, ctx->out_len.as<uint64_t>(), ctx->out_s.as<int64_t>(), ctx->M, G,
+                                        ids.data(), (uint32_t)ids.size(), eliminate_both != 0, &n, ctx->stream));
+    HIPCHK(ctx->flen.ensure((n + 1) * 8));
+    HIPCHK(ctx->fs.ensure((n + 1) * (size_t)G * 8 + 8));
+    HIPCHK(eo_gather(ctx->eo, G, ctx->flen.as<uint64_t>(), ctx->fs.as<int64_t>(), ctx->stream));
+    std::swap(ctx->out_len, ctx->flen);
+    std::swap(ctx->out_s, ctx->fs);
+    ctx->M = n;
+    return MUMS_OK;
+}
+
 // a caller's MatchList becomes the context's result (filters / EliminateOverlaps input)
 int mums_load_matches(mums_ctx* ctx, uint32_t seq_count, uint64_t count, const uint64_t* lengths,
                       const int64_t* starts) {

@@ -417,6 +417,7 @@ struct EoWork {
     void *nsw = nullptr, *scratch = nullptr, *plen = nullptr, *ps = nullptr, *nm_key = nullptr, *nm_id = nullptr;
     void *nk2 = nullptr, *nv2 = nullptr, *nk3 = nullptr, *nv3 = nullptr, *radix = nullptr, *ctr = nullptr;
     uint64_t cap_n = 0, cap_pool = 0, cap_new = 0, pool_n = 0, n_final = 0;
+    int pool_G = 0;   // sequence count the pool's start rows were sized for
     unsigned long long hbuf[8] = {};
     EoWork() = default;
     EoWork(const EoWork&) = delete;
@@ -427,6 +428,12 @@ struct EoWork {
 // the result stays in w (pool + ids) until eo_gather writes it out (*M_out matches)
 hipError_t eliminate_overlaps_device(EoWork& w, const uint64_t* d_len, const int64_t* d_s, uint64_t M, int G,
                                      uint64_t* M_out, hipStream_t st);
+// EliminateOverlaps_v2 (ProgressiveAligner.h:300-406): the passes run over seq_ids (host array,
+// in order, repeats allowed, every id < G); nothing is appended (processNewMatch, :260-271,
+// never keeps a copy of an ungapped Match), so *M_out <= M.  Result read with eo_gather.
+hipError_t eliminate_overlaps_v2_device(EoWork& w, const uint64_t* d_len, const int64_t* d_s, uint64_t M, int G,
+                                        const uint32_t* seq_ids, uint32_t nids, bool eliminate_both, uint64_t* M_out,
+                                        hipStream_t st);
 hipError_t eo_gather(EoWork& w, int G, uint64_t* d_len_out, int64_t* d_s_out, hipStream_t st);
 // libstdc++ std::sort replay of ids 0..n-1 by d_keys (test entry point); depth_override >= 0
 // forces __introsort_loop's depth limit

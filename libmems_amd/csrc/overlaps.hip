@@ -395,6 +395,80 @@ __global__ void cluster_sim_kernel(uint32_t* V, int64_t* plen, int64_t* ps, int 
     if (keeps) atomicAdd(nkeep, keeps);
 }
 
+// checkConsistent (ProgressiveAligner.h:272-291): the same b->Start - a->Start in every
+// sequence where both are defined, and more than one such sequence
+__device__ __forceinline__ bool check_consistent(const int64_t* a, const int64_t* b, int G) {
+    bool consistent = true, have = false;
+    int64_t o = 0;
+    int inter = 0;
+    for (int g = 0; g < G; ++g) {
+        if (a[g] == 0 || b[g] == 0) continue;
+        ++inter;
+        if (!have) {
+            o = b[g] - a[g];
+            have = true;
+        }
+        if (o != b[g] - a[g]) consistent = false;
+    }
+    return consistent && inter > 1;
+}
+
+// EliminateOverlaps_v2's matchI / nextI loops (ProgressiveAligner.h:319-382) over one cluster.
+// Length(seqI) (UngappedLocalAlignment.h:48-55) is m_length here: every match of a cluster is
+// defined in seqI.  CropRight / CropLeft(diff, seqI) (:169-184) take the orientation of seqI.
+// processNewMatch (:260-271) sets Start(seqI) to NO_MATCH and then asks for Length(seqI) > 0,
+// which is 0 for a Match: the cut-off copy is never kept, so none is made here.
+__global__ void cluster_sim_v2_kernel(uint32_t* V, int64_t* plen, int64_t* ps, int G, int seqI,
+                                      const uint32_t* __restrict__ cstart, uint32_t C, int eliminate_both,
+                                      unsigned long long* __restrict__ ndel) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const int64_t a = cstart[c], b = cstart[c + 1];
+    if (b - a < 2) return;
+    unsigned long long dels = 0;
+    for (int64_t mi = a; mi < b; mi++) {
+        if (V[mi] == kDel) continue;
+        for (int64_t nj = mi + 1; nj < b; nj++) {
+            if (V[nj] == kDel) continue;
+            bool deleted_i = false;
+            const uint64_t I = V[mi], J = V[nj];
+            int64_t* sI = ps + I * G;
+            int64_t* sJ = ps + J * G;
+            const int64_t startI = sI[seqI], lenI = plen[I], startJ = sJ[seqI];
+            int64_t diff = (startJ < 0 ? -startJ : startJ) - (startI < 0 ? -startI : startI) - lenI;
+            if (diff >= 0) break;   // there are no more overlaps
+            diff = -diff;
+            // both decided before any crop of the pair
+            const int mJ = mult_of(sJ, G), mI = mult_of(sI, G);
+            const bool i_smaller = mJ > mI || (mJ == mI && plen[J] > lenI);
+            const bool both = eliminate_both && !check_consistent(sI, sJ, G);
+            if (both || i_smaller) {   // :345
+                if (diff >= lenI) {
+                    V[mi] = kDel;
+                    deleted_i = true;
+                    ++dels;
+                } else if (startI > 0) {
+                    crop_end(&plen[I], sI, G, diff);     // CropRight, forward
+                } else {
+                    crop_start(&plen[I], sI, G, diff);   // CropRight, reverse
+                }
+            }
+            if (both || !i_smaller) {   // :363 (runs on nextI also after matchI was deleted)
+                if (diff >= plen[J]) {
+                    V[nj] = kDel;
+                    ++dels;
+                } else if (startJ > 0) {
+                    crop_start(&plen[J], sJ, G, diff);   // CropLeft, forward
+                } else {
+                    crop_end(&plen[J], sJ, G, diff);     // CropLeft, reverse
+                }
+            }
+            if (deleted_i) break;
+        }
+    }
+    if (dels) atomicAdd(ndel, dels);
+}
+
 __global__ void keep_kernel(const uint32_t* __restrict__ V, uint32_t n, uint32_t* __restrict__ keep) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i <= n) keep[i] = (i < n && V[i] != kDel) ? 1u : 0u;
@@ -557,70 +631,107 @@ hipError_t eo_sort_ids(EoWork& w, const uint64_t* d_keys, uint32_t n, int depth_
     return hipStreamSynchronize(st);
 }
 
-hipError_t eliminate_overlaps_device(EoWork& w, const uint64_t* d_len, const int64_t* d_s, uint64_t M, int G,
-                                     uint64_t* M_out, hipStream_t st) {
-    if (M >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
+// pool capacity for `need` matches of G starts; the first pool_n entries survive a growth
+static hipError_t ensure_pool(EoWork& w, uint64_t need, int G, hipStream_t st) {
+    if (need <= w.cap_pool && G <= w.pool_G) return hipSuccess;
+    const uint64_t c = std::max(need + (need >> 1) + 1024, w.cap_pool);
+    void *nl = nullptr, *ns = nullptr;
+    EOCHK(hipMalloc(&nl, c * 8));
+    EOCHK(hipMalloc(&ns, c * (uint64_t)G * 8));
+    if (w.plen && w.pool_n) {
+        EOCHK(hipMemcpyAsync(nl, w.plen, w.pool_n * 8, hipMemcpyDeviceToDevice, st));
+        EOCHK(hipMemcpyAsync(ns, w.ps, w.pool_n * (uint64_t)G * 8, hipMemcpyDeviceToDevice, st));
+        EOCHK(hipStreamSynchronize(st));
+    }
+    if (w.plen) (void)hipFree(w.plen);
+    if (w.ps) (void)hipFree(w.ps);
+    w.plen = nl;
+    w.ps = ns;
+    w.cap_pool = c;
+    w.pool_G = G;
+    return hipSuccess;
+}
+
+// pool = the M input matches, V = their ids in MatchList order
+static hipError_t init_pool(EoWork& w, const uint64_t* d_len, const int64_t* d_s, uint64_t M, int G, hipStream_t st) {
     EOCHK(ensure_n(w, M, st));
-    unsigned long long* hl = (unsigned long long*)w.hbuf;
-    // pool: the M input matches, new ones appended pass by pass
-    auto ensure_pool = [&](uint64_t need) -> hipError_t {
-        if (need <= w.cap_pool) return hipSuccess;
-        const uint64_t c = need + (need >> 1) + 1024;
-        void *nl = nullptr, *ns = nullptr;
-        EOCHK(hipMalloc(&nl, c * 8));
-        EOCHK(hipMalloc(&ns, c * (uint64_t)G * 8));
-        if (w.plen && w.pool_n) {
-            EOCHK(hipMemcpyAsync(nl, w.plen, w.pool_n * 8, hipMemcpyDeviceToDevice, st));
-            EOCHK(hipMemcpyAsync(ns, w.ps, w.pool_n * (uint64_t)G * 8, hipMemcpyDeviceToDevice, st));
-            EOCHK(hipStreamSynchronize(st));
-        }
-        if (w.plen) (void)hipFree(w.plen);
-        if (w.ps) (void)hipFree(w.ps);
-        w.plen = nl;
-        w.ps = ns;
-        w.cap_pool = c;
-        return hipSuccess;
-    };
     w.pool_n = 0;
-    EOCHK(ensure_pool(M + 1));
+    EOCHK(ensure_pool(w, M + 1, G, st));
     if (M > 0)
         hipLaunchKernelGGL(init_pool_kernel, dim3(grid_of(M)), dim3(kBlock), 0, st, d_len, d_s, M, G,
                            (int64_t*)w.plen, (int64_t*)w.ps, (uint32_t*)w.V);
     EOCHK(hipGetLastError());
     w.pool_n = M;
+    return hipSuccess;
+}
+
+// counters of one pass, in w.ctr from byte 64: pair bound, new matches, deleted, kept
+static unsigned long long* pass_counters(EoWork& w) { return (unsigned long long*)w.ctr + 8; }
+
+// the start of a pass over sequence seqI, shared by both versions: V[0, n) sorted by
+// SingleStartComparator(seqI) in libstdc++'s order, then the clusters of the defined part:
+// *C_out clusters, cluster c = [cstart[c], cstart[c + 1]) with cstart in w.fr.  The pass
+// counters are zeroed.
+static hipError_t pass_clusters(EoWork& w, uint64_t n, int G, int seqI, uint32_t* C_out, hipStream_t st) {
+    EOCHK(ensure_n(w, n, st));
+    unsigned long long* hl = (unsigned long long*)w.hbuf;
+    uint32_t* V = (uint32_t*)w.V;
+    uint64_t* K = (uint64_t*)w.K;
+    hipLaunchKernelGGL(keys_kernel, dim3(grid_of(n)), dim3(kBlock), 0, st, V, (const int64_t*)w.ps, G, seqI,
+                       (uint32_t)n, K);
+    EOCHK(hipGetLastError());
+    EOCHK(std_sort_device(w, (uint32_t)n, -1, st));
+    // clusters of the defined part
+    const uint32_t T = (uint32_t)((n + kEoTile - 1) / kEoTile);
+    uint64_t* tmax = (uint64_t*)((char*)w.scratch + scan_tmp_bytes(2 * w.cap_n + 2));
+    uint32_t* flag = (uint32_t*)w.fl;
+    hipLaunchKernelGGL(tile_max_kernel, dim3(T), dim3(kBlock), 0, st, K, V, (const int64_t*)w.plen, (uint32_t)n,
+                       tmax);
+    hipLaunchKernelGGL(tile_prefix_kernel, dim3(1), dim3(64), 0, st, tmax, T);
+    hipLaunchKernelGGL(heads_kernel, dim3(T), dim3(64), 0, st, K, V, (const int64_t*)w.plen, (uint32_t)n,
+                       (const uint64_t*)tmax, flag);
+    EOCHK(hipGetLastError());
+    uint32_t* d_C = (uint32_t*)w.ctr + 8;
+    EOCHK(exclusive_scan_u32(flag, n + 1, w.scratch, d_C, st));
+    EOCHK(hipMemsetAsync(pass_counters(w), 0, 32, st));
+    EOCHK(hipMemcpyAsync(hl, d_C, 4, hipMemcpyDeviceToHost, st));
+    EOCHK(hipStreamSynchronize(st));
+    const uint32_t C = (uint32_t)(hl[0] & 0xFFFFFFFFull);
+    hipLaunchKernelGGL(cluster_starts_kernel, dim3(grid_of(n + 1)), dim3(kBlock), 0, st, flag, (uint32_t)n,
+                       (uint32_t*)w.fr, C);
+    *C_out = C;
+    return hipGetLastError();
+}
+
+// the ids of V[0, n) that were not deleted, order kept (V and V2 change places)
+static hipError_t compact_deleted(EoWork& w, uint64_t n, hipStream_t st) {
+    uint32_t* keep = (uint32_t*)w.fl;
+    hipLaunchKernelGGL(keep_kernel, dim3(grid_of(n + 1)), dim3(kBlock), 0, st, (const uint32_t*)w.V, (uint32_t)n, keep);
+    EOCHK(exclusive_scan_u32(keep, n + 1, w.scratch, nullptr, st));
+    hipLaunchKernelGGL(compact_ids_kernel, dim3(grid_of(n)), dim3(kBlock), 0, st, (const uint32_t*)w.V, keep,
+                       (uint32_t)n, (uint32_t*)w.V2);
+    EOCHK(hipGetLastError());
+    std::swap(w.V, w.V2);
+    return hipSuccess;
+}
+
+hipError_t eliminate_overlaps_device(EoWork& w, const uint64_t* d_len, const int64_t* d_s, uint64_t M, int G,
+                                     uint64_t* M_out, hipStream_t st) {
+    if (M >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
+    unsigned long long* hl = (unsigned long long*)w.hbuf;
+    // pool: the M input matches, new ones appended pass by pass
+    EOCHK(init_pool(w, d_len, d_s, M, G, st));
     uint64_t n = M;
     if (M >= 2) {   // if( ml.size() < 2 ) return;
         for (int seqI = 0; seqI < G; ++seqI) {
-            EOCHK(ensure_n(w, n, st));
+            uint32_t C = 0;
+            EOCHK(pass_clusters(w, n, G, seqI, &C, st));
             uint32_t* V = (uint32_t*)w.V;
-            uint64_t* K = (uint64_t*)w.K;
-            hipLaunchKernelGGL(keys_kernel, dim3(grid_of(n)), dim3(kBlock), 0, st, V, (const int64_t*)w.ps, G, seqI,
-                               (uint32_t)n, K);
-            EOCHK(hipGetLastError());
-            EOCHK(std_sort_device(w, (uint32_t)n, -1, st));
-            // clusters of the defined part
-            const uint32_t T = (uint32_t)((n + kEoTile - 1) / kEoTile);
-            uint64_t* tmax = (uint64_t*)((char*)w.scratch + scan_tmp_bytes(2 * w.cap_n + 2));
-            uint32_t* flag = (uint32_t*)w.fl;
-            hipLaunchKernelGGL(tile_max_kernel, dim3(T), dim3(kBlock), 0, st, K, V, (const int64_t*)w.plen,
-                               (uint32_t)n, tmax);
-            hipLaunchKernelGGL(tile_prefix_kernel, dim3(1), dim3(64), 0, st, tmax, T);
-            hipLaunchKernelGGL(heads_kernel, dim3(T), dim3(64), 0, st, K, V, (const int64_t*)w.plen, (uint32_t)n,
-                               (const uint64_t*)tmax, flag);
-            EOCHK(hipGetLastError());
-            uint32_t* d_C = (uint32_t*)w.ctr + 8;
-            EOCHK(exclusive_scan_u32(flag, n + 1, w.scratch, d_C, st));
-            unsigned long long* d_cap = (unsigned long long*)w.ctr + 8;   // bytes 64..
+            uint32_t* cstart = (uint32_t*)w.fr;
+            unsigned long long* d_cap = pass_counters(w);
             unsigned long long* d_nnew = d_cap + 1;
             unsigned long long* d_ndel = d_cap + 2;
             unsigned long long* d_nkeep = d_cap + 3;
-            EOCHK(hipMemsetAsync(d_cap, 0, 32, st));
-            EOCHK(hipMemcpyAsync(hl, d_C, 4, hipMemcpyDeviceToHost, st));
-            EOCHK(hipStreamSynchronize(st));
-            const uint32_t C = (uint32_t)(hl[0] & 0xFFFFFFFFull);
-            uint32_t* cstart = (uint32_t*)w.fr;
-            hipLaunchKernelGGL(cluster_starts_kernel, dim3(grid_of(n + 1)), dim3(kBlock), 0, st, flag, (uint32_t)n,
-                               cstart, C);
             if (C > 0)
                 hipLaunchKernelGGL(cluster_bound_kernel, dim3(grid_of(C)), dim3(kBlock), 0, st, cstart, C, d_cap);
             EOCHK(hipGetLastError());
@@ -628,7 +739,7 @@ hipError_t eliminate_overlaps_device(EoWork& w, const uint64_t* d_len, const int
             EOCHK(hipStreamSynchronize(st));
             const uint64_t bound_new = hl[0];
             if (bound_new == 0) continue;   // no overlapping pair: nothing changes this pass
-            EOCHK(ensure_pool(w.pool_n + bound_new + 1));
+            EOCHK(ensure_pool(w, w.pool_n + bound_new + 1, G, st));
             if (bound_new + 2 > w.cap_new) {
                 const uint64_t c = bound_new + (bound_new >> 1) + 1024;
                 EOCHK(grow(&w.nm_key, c * 8));
@@ -650,13 +761,7 @@ hipError_t eliminate_overlaps_device(EoWork& w, const uint64_t* d_len, const int
             w.pool_n += nnew_all;
             uint64_t wn = n;
             if (ndel > 0) {
-                uint32_t* keep = (uint32_t*)w.fl;
-                hipLaunchKernelGGL(keep_kernel, dim3(grid_of(n + 1)), dim3(kBlock), 0, st, V, (uint32_t)n, keep);
-                EOCHK(exclusive_scan_u32(keep, n + 1, w.scratch, nullptr, st));
-                hipLaunchKernelGGL(compact_ids_kernel, dim3(grid_of(n)), dim3(kBlock), 0, st, V, keep, (uint32_t)n,
-                                   (uint32_t*)w.V2);
-                EOCHK(hipGetLastError());
-                std::swap(w.V, w.V2);
+                EOCHK(compact_deleted(w, n, st));
                 wn = n - ndel;
             }
             if (nkeep > 0) {   // new matches in (cluster, creation) order; dropped copies last
@@ -671,6 +776,44 @@ hipError_t eliminate_overlaps_device(EoWork& w, const uint64_t* d_len, const int
                 EOCHK(hipMemcpyAsync((uint32_t*)w.V + wn, sv, nkeep * 4, hipMemcpyDeviceToDevice, st));
             }
             n = wn + nkeep;
+        }
+    }
+    *M_out = n;
+    w.n_final = n;
+    return hipStreamSynchronize(st);
+}
+
+// EliminateOverlaps_v2 (ProgressiveAligner.h:300-406).  Per id of seq_ids the same pass start
+// as above (the cluster-head kernels read plen as the length: for the defined part of the
+// sorted list Length(seqI) equals m_length, so they serve v2 as they are), then the v2 walk.
+// Nothing is appended (see cluster_sim_v2_kernel), so the pool stays at the M input matches.
+hipError_t eliminate_overlaps_v2_device(EoWork& w, const uint64_t* d_len, const int64_t* d_s, uint64_t M, int G,
+                                        const uint32_t* seq_ids, uint32_t nids, bool eliminate_both, uint64_t* M_out,
+                                        hipStream_t st) {
+    if (M >= 0xFFFFFFF0ull || (nids && !seq_ids)) return hipErrorInvalidValue;
+    for (uint32_t k = 0; k < nids; ++k)
+        if (seq_ids[k] >= (uint32_t)G) return hipErrorInvalidValue;
+    unsigned long long* hl = (unsigned long long*)w.hbuf;
+    EOCHK(init_pool(w, d_len, d_s, M, G, st));
+    uint64_t n = M;
+    if (M >= 2) {   // if( ml.size() < 2 ) return;
+        for (uint32_t sidI = 0; sidI < nids && n > 0; ++sidI) {
+            const int seqI = (int)seq_ids[sidI];
+            uint32_t C = 0;
+            EOCHK(pass_clusters(w, n, G, seqI, &C, st));
+            if (C == 0) continue;   // no match is defined in seqI
+            unsigned long long* d_ndel = pass_counters(w) + 2;
+            hipLaunchKernelGGL(cluster_sim_v2_kernel, dim3(grid_of(C)), dim3(kBlock), 0, st, (uint32_t*)w.V,
+                               (int64_t*)w.plen, (int64_t*)w.ps, G, seqI, (const uint32_t*)w.fr, C,
+                               eliminate_both ? 1 : 0, d_ndel);
+            EOCHK(hipGetLastError());
+            EOCHK(hipMemcpyAsync(hl, d_ndel, 8, hipMemcpyDeviceToHost, st));
+            EOCHK(hipStreamSynchronize(st));
+            const uint64_t ndel = hl[0];
+            if (ndel > 0) {
+                EOCHK(compact_deleted(w, n, st));
+                n -= ndel;
+            }
         }
     }
     *M_out = n;
