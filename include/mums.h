@@ -131,8 +131,28 @@ int  mums_add_genome_device(mums_ctx* ctx, const void* d_ascii, uint64_t n);
  * mums::HipSML in mums_memhash.hpp) hands its genome to a MemHash context this way, through
  * mums_add_genome_device, without a host copy.  Valid until the context is cleared. */
 int  mums_genome_device(mums_ctx* ctx, uint32_t genome, const void** d_ascii, uint64_t* n);
-/* MemHash::Clear / ClearSequences (MemHash.cpp:80-93): drops genomes and results. */
+/* MemHash::Clear (MemHash.cpp:76-93): drops genomes, results and a kept hash table. */
 int  mums_clear(mums_ctx* ctx);
+/* MemHash::ClearSequences (MemHash.cpp:71-74): drops the genomes, keeps the hash table.
+ * The context keeps the table of its last completed FindMatches (every bucket's entries in
+ * vector order), mem_table_count, MemCount, MemCollisionCount and all settings; the next
+ * mums_find / mums_find_stage(MUMS_STAGE_ALL) replays its AddHashEntry calls (newly added
+ * genomes, current seed) onto that table and returns the whole table (GetMatchList walks all
+ * buckets, MemHash.h:182-203) -- progressiveMauve's seed families (ProgressiveAligner.cpp:
+ * 619-653).  mem_count, collision_count and mums_mem_table_count are then cumulative since the
+ * last mums_clear; probes, groups, seedmers, timings and the match log describe the last find.
+ * Without this call a second mums_find starts from an empty table.  MUMS_STAGE_SEEDS runs
+ * neither use nor disturb the kept table.
+ * mums_mem_table_count after this call returns the kept table's counts.  mums_set_params with
+ * another table size between the find and this call empties that find's table, as
+ * MemHash::SetTableSize does (MemHash.cpp:95-102): nothing is kept then.
+ * MUMS_OK with an empty table when no find completed.  MUMS_E_INVALID (nothing changes) when
+ * a filter, EliminateOverlaps or mums_load_matches edited the context's list since the find:
+ * the kept table is the hash table, not the caller's list.  With a non-empty kept table:
+ * mums_set_params with another table size and a find with another genome count are
+ * MUMS_E_INVALID; the ParallelMemHash compat mode, sharded contexts, the chunked mode (above
+ * 2^32 seed-mers) and the sliced FindMatches are MUMS_E_UNSUPPORTED, the table left intact. */
+int  mums_clear_sequences(mums_ctx* ctx);
 
 /* MemHash::FindMatchesFromPosition (MemHash.cpp:117-127) -> FindMatchSeeds(start_points)
  * (MatchFinder.cpp:137-164): the merge of the next finds starts at SML index

@@ -221,14 +221,18 @@ public:
     MemHash(const MemHash&) = delete;
     MemHash& operator=(const MemHash&) = delete;
 
-    // MemHash::Clear / ClearSequences (MemHash.cpp:80-93)
+    // MemHash::Clear (MemHash.cpp:76-93): genomes, results and the hash table
     virtual void Clear() { check(mums_clear(ctx_)); }
-    virtual void ClearSequences() { Clear(); }
+    // MemHash::ClearSequences (MemHash.cpp:71-74): the genomes only; the next FindMatches hashes
+    // onto the kept table (pairwiseAnchorSearch's seed families, ProgressiveAligner.cpp:619-653)
+    virtual void ClearSequences() { check(mums_clear_sequences(ctx_)); }
     // MemHash::SetTableSize (MemHash.cpp:95-102), tolerances (MemHash.h:125-144)
-    void SetTableSize(uint32_t n) { table_size_ = n; push_params(); }
-    void SetRepeatTolerance(uint32_t t) { repeat_tol_ = t; push_params(); }
+    // (the stored value changes only when the library took it: a refused table size must not be
+    // re-sent by the next tolerance setter)
+    void SetTableSize(uint32_t n) { push_params(repeat_tol_, enum_tol_, n); }
+    void SetRepeatTolerance(uint32_t t) { push_params(t, enum_tol_, table_size_); }
     uint32_t GetRepeatTolerance() const { return repeat_tol_; }
-    void SetEnumerationTolerance(uint32_t t) { enum_tol_ = t; push_params(); }
+    void SetEnumerationTolerance(uint32_t t) { push_params(repeat_tol_, t, table_size_); }
     uint32_t GetEnumerationTolerance() const { return enum_tol_; }
     // seed pattern the SMLs are sorted on (SortedMerList::Create; 0 = default weight)
     void SetSeed(uint64_t pattern) { check(mums_set_seed(ctx_, pattern)); }
@@ -407,7 +411,12 @@ protected:
         if (rc == MUMS_E_GAP) throw GapInSequence(msg);
         throw InvalidData(msg);
     }
-    void push_params() { check(mums_set_params(ctx_, repeat_tol_, enum_tol_, table_size_)); }
+    void push_params(uint32_t repeat_tol, uint32_t enum_tol, uint32_t table_size) {
+        check(mums_set_params(ctx_, repeat_tol, enum_tol, table_size));
+        repeat_tol_ = repeat_tol;
+        enum_tol_ = enum_tol;
+        table_size_ = table_size;
+    }
     void add_list(MatchList& ml) {
         if (ml.sml_table.empty()) {
             for (const auto& s : ml.seq_table) AddSequence(s);

@@ -110,7 +110,7 @@ EXPORTED_SYMBOLS = [
     "mums_shard_restart_info", "mums_shard_tie_flags", "mums_shard_tie_replay", "mums_shard_tie_apply",
     "mums_genome_device", "mums_shard_chain_label", "mums_shard_chain_export", "mums_shard_find_labelled",
     "mums_shard_chain_info", "mums_shard_chain_entries", "mums_shard_entry_thresholds", "mums_shard_kept_export",
-    "mums_shard_find_kept", "mums_comm_exchange_info", "mums_eliminate_overlaps_v2",
+    "mums_shard_find_kept", "mums_comm_exchange_info", "mums_eliminate_overlaps_v2", "mums_clear_sequences",
 ]
 
 # mums_comm_ops (include/mums.h): the caller's transport as two host callbacks
@@ -162,6 +162,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mums_shard_find_kept.argtypes = [vp, vp, vp, u64, vp, vp, u64, u32, vp, vp, u64, vp]
     lib.mums_comm_exchange_info.argtypes = [vp, vp]
     lib.mums_clear.argtypes = [vp]
+    lib.mums_clear_sequences.argtypes = [vp]
     lib.mums_find.argtypes = [vp]
     lib.mums_find_stage.argtypes = [vp, i32]
     lib.mums_result_count.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u32)]
@@ -326,17 +327,19 @@ class MemHash:
             raise MumsError(rc, msg)
 
     # ---- configuration (MemHash.h:72, 125-144; MaskedMemHash.h:32) ------------
+    # (a value is stored only once the library took it: a refused table size must not be
+    # re-sent by the next tolerance setter)
     def SetTableSize(self, n: int) -> None:
-        self._ts = n
         self._check(self._lib.mums_set_params(self._ctx, getattr(self, "_rt", 0), getattr(self, "_et", 1), n))
+        self._ts = n
 
     def SetRepeatTolerance(self, t: int) -> None:
-        self._rt = t
         self._check(self._lib.mums_set_params(self._ctx, t, self._et, self._ts))
+        self._rt = t
 
     def SetEnumerationTolerance(self, t: int) -> None:
-        self._et = t
         self._check(self._lib.mums_set_params(self._ctx, self._rt, t, self._ts))
+        self._et = t
 
     def SetSeed(self, pattern: int) -> None:
         """Seed pattern the SortedMerLists are built with (0 = default weight for the genome lengths)."""
@@ -365,7 +368,11 @@ class MemHash:
         self._keepalive.clear()
         self._check(self._lib.mums_clear(self._ctx))
 
-    ClearSequences = Clear
+    def ClearSequences(self) -> None:
+        """MemHash::ClearSequences (MemHash.cpp:71-74): the genomes go, the hash table stays --
+        the next FindMatches hashes onto it (seed families, ProgressiveAligner.cpp:619-653)."""
+        self._check(self._lib.mums_clear_sequences(self._ctx))
+        self._keepalive.clear()
 
     # ---- compute -----------------------------------------------------------------
     def FindMatches(self, sequences: Optional[Sequence] = None) -> MatchList:

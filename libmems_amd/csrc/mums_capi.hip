@@ -144,6 +144,21 @@ struct mums_ctx {
     DevBuf labx;             // sharded chain export scratch (mums_shard_chain_export)
     uint32_t* emit_tbl = nullptr;          // bucket vectors / slice bases of the last replay
     const uint32_t* emit_base = nullptr;   // (chunked: compacted, in cbuf; else tbl / bstart)
+    // MemHash::ClearSequences (mums_clear_sequences): the hash table kept for the next find
+    DevBuf keep_pool, keep_cnt;   // its entries {length, offset, starts} bucket-major in vector order; per-bucket counts
+    bool keep_on = false;         // ClearSequences since the last Clear: the next find hashes onto the kept table
+    uint64_t keep_n = 0;          // kept entries
+    int keep_G = 0;               // their seq_count
+    uint32_t keep_T = 0;          // the table size they were hashed with
+    uint64_t keep_coll = 0;       // MemCollisionCount up to the kept table
+    uint32_t pool_c = 0;          // this find: carried entries at the front of ctx->pool
+    uint64_t carry_coll = 0;      // this find: collisions of the earlier finds (fill_stats)
+    bool table_fresh = false;     // out_len / out_s / tsize are the hash table of a completed find
+    uint64_t fresh_M = 0;         // that find's entries, seq_count, table size and cumulative collisions
+    int fresh_G = 0;
+    uint32_t fresh_T = 0;
+    uint64_t fresh_coll = 0;
+    bool list_edited = false;     // a filter / EliminateOverlaps / load_matches changed the list since
     EoWork eo;               // EliminateOverlaps work arrays (overlaps.hip)
     bool match_log = false;  // MemHash::SetMatchLog: record the inserts (replay.hip)
     uint64_t log_n = 0;
@@ -353,7 +368,8 @@ int find_rows(mums_ctx* ctx, MatProbes v, const uint32_t* packed, const MatchPar
     // the replay's keep pass reads them in line order, no per-probe chain id is scattered
     HIPCHK((launch_chains<MG, MatProbes>(v, nullptr, P, ctx->gt, mp, ctx->ss, packed,
                                     ctx->chain_tmp.p, ctx->tmp.p, ctx->radix_tmp.p, nullptr,
-                                    ctx->pool.as<int64_t>(), &dc->nchains, st, dc,
+                                    ctx->pool.as<int64_t>() + (uint64_t)ctx->pool_c * (uint64_t)(ctx->gt.G + 2),
+                                    &dc->nchains, st, dc,
                                     ctx->profiling ? ctx->ev_walk : nullptr, ctx->fk.as<uint32_t>(), 0u,
                                     v.fs != nullptr, ctx->chain_of.as<uint32_t>())));
     return find_replay<MG>(ctx, v, mp, st);
@@ -382,11 +398,19 @@ int find_replay(mums_ctx* ctx, MatProbes v, const MatchParams& mp, hipStream_t s
     }
     // the fullest bucket's vector in LDS when it fits (it holds <= its probes)
     const uint32_t lds_cap = std::max<uint32_t>(64, std::min<uint32_t>(ctx->hc.max_bucket, kReplayLdsIds));
-    HIPCHK((launch_replay_kept<MG, MatProbes>(v, ctx->gt, mp, ctx->L, P, ctx->pool.as<int64_t>(), nullptr,
-                                         ctx->fk.as<uint32_t>(), ctx->hc.nchains,
-                                         ctx->chain_tmp.p, ctx->radix_tmp.p, ctx->tmp.p, lds_cap,
-                                         ctx->tsize.as<uint32_t>(), ctx->counters.p, dbg, st, mlog, &ctx->emit_tbl,
-                                         &ctx->emit_base, devbuf_alloc, &ctx->cbuf, ctx->chain_of.as<uint32_t>())));
+    if (ctx->pool_c) {   // onto the table ClearSequences kept: every probe against the carried vectors
+        HIPCHK((launch_replay_carried<MG, MatProbes>(v, ctx->gt, mp, ctx->L, P, ctx->pool.as<int64_t>(), ctx->pool_c,
+                                                     ctx->keep_cnt.as<uint32_t>(), P ? ctx->hc.nchains : 0u,
+                                                     ctx->chain_of.as<uint32_t>(), kReplayLdsIds,
+                                                     ctx->tsize.as<uint32_t>(), ctx->counters.p, st, mlog,
+                                                     &ctx->emit_tbl, &ctx->emit_base, devbuf_alloc, &ctx->cbuf)));
+    } else {
+        HIPCHK((launch_replay_kept<MG, MatProbes>(v, ctx->gt, mp, ctx->L, P, ctx->pool.as<int64_t>(), nullptr,
+                                                  ctx->fk.as<uint32_t>(), ctx->hc.nchains, ctx->chain_tmp.p,
+                                                  ctx->radix_tmp.p, ctx->tmp.p, lds_cap, ctx->tsize.as<uint32_t>(),
+                                                  ctx->counters.p, dbg, st, mlog, &ctx->emit_tbl, &ctx->emit_base,
+                                                  devbuf_alloc, &ctx->cbuf, ctx->chain_of.as<uint32_t>())));
+    }
     if (mlog) {   // the inserts in AddHashEntry call order (probe index << 32 | chain)
         HIPCHK(hipMemcpyAsync(&ctx->hc, dc, sizeof(DevCounters), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -415,6 +439,40 @@ int find_replay(mums_ctx* ctx, MatProbes v, const MatchParams& mp, hipStream_t s
                     (unsigned long)d[3], d[4] / 100.0, d[5] / 100.0, d[6] / 100.0, d[7] / 100.0);
         }
     }
+    return MUMS_OK;
+}
+
+int find_replay_dispatch(mums_ctx* ctx, MatProbes v, const MatchParams& mp, hipStream_t st) {
+    const int G = ctx->gt.G;
+    if (G <= 4) return find_replay<4>(ctx, v, mp, st);
+    if (G <= 8) return find_replay<8>(ctx, v, mp, st);
+    if (G <= 16) return find_replay<16>(ctx, v, mp, st);
+    if (G <= 32) return find_replay<32>(ctx, v, mp, st);
+    return find_replay<64>(ctx, v, mp, st);
+}
+
+// a FindMatches onto a non-empty table kept by ClearSequences: every mode and shape that
+// cannot replay onto it, decided before the table is touched.  big: the chunked mode (known
+// when the find starts); sliced: the sliced / prelabelled FindMatches (known in find_tail)
+int carried_refusal(mums_ctx* ctx, bool big, bool sliced) {
+    const std::string what = "FindMatches onto a table kept by ClearSequences: ";
+    const char* drop = " (mums_clear drops the table)";
+    if (ctx->pcompat)
+        return fail(ctx, MUMS_E_UNSUPPORTED, what + "the ParallelMemHash compat mode is not supported" + drop);
+    if (ctx->shard || ctx->prelabelled)
+        return fail(ctx, MUMS_E_UNSUPPORTED, what + "a sharded context is not supported");
+    if (big)
+        return fail(ctx, MUMS_E_UNSUPPORTED, what + "the chunked mode (above 2^32 seed-mers, or MUMS_DEV_CHUNK_RECORDS) "
+                                                    "is not supported" + drop);
+    if (sliced)
+        return fail(ctx, MUMS_E_UNSUPPORTED, what + "the sliced FindMatches is not supported" + drop);
+    if (ctx->gt.G != ctx->keep_G)
+        return fail(ctx, MUMS_E_INVALID, what + "the kept entries have " + std::to_string(ctx->keep_G) +
+                                             " sequences, this find " + std::to_string(ctx->gt.G));
+    if (ctx->table_size != ctx->keep_T)
+        return fail(ctx, MUMS_E_INVALID, what + "the table size differs from the kept table's");
+    if ((uint64_t)ctx->keep_n + ctx->P >= 0xFFFFFFF0ull)
+        return fail(ctx, MUMS_E_UNSUPPORTED, what + "more than 2^32 kept entries and seed probes");
     return MUMS_OK;
 }
 
@@ -682,6 +740,15 @@ int find_tail(mums_ctx* ctx, const MatchParams& mp, const uint32_t* packed, Rows
     // prelabelled (sharded FindMatches): the ranks labelled the chains of their own probes;
     // their entries are merged and replayed like the slices of the sliced path
     const bool chunked = ctx->P > fchunk || ctx->prelabelled;
+    // onto the table ClearSequences kept (refused before anything of it is touched)
+    const bool carried = ctx->keep_on && ctx->keep_n > 0;
+    if (carried) {
+        const int rc = carried_refusal(ctx, ctx->rec_ib > 32, chunked);
+        if (rc) return rc;
+    }
+    ctx->table_fresh = false;
+    ctx->pool_c = carried ? (uint32_t)ctx->keep_n : 0u;
+    ctx->carry_coll = ctx->keep_on ? ctx->keep_coll : 0;
     HIPCHK(ctx->chain_of.ensure((ctx->P + 1) * (chunked ? 4 : 12)));   // find_rows: 3 words per line position
     // the replay keeps only the chain-first / suspicious probes (launch_replay_kept): its
     // summaries, bucket vectors and spill live in ctx->cbuf, sized by their count
@@ -689,8 +756,11 @@ int find_tail(mums_ctx* ctx, const MatchParams& mp, const uint32_t* packed, Rows
     if (chunked) {   // find_rows_chunked: chains per slice, merged
         ctx->pool.release();
     } else {
-        HIPCHK(ctx->pool.ensure((ctx->P + 1) * (size_t)(G + 2) * 8));
+        HIPCHK(ctx->pool.ensure((ctx->pool_c + ctx->P + 1) * (size_t)(G + 2) * 8));
         HIPCHK(ctx->chain_tmp.ensure(chain_tmp_bytes(ctx->P + 1, Tb, G)));
+        if (carried)   // the carried entries lead the pool; the chains' entries follow (find_rows)
+            HIPCHK(hipMemcpyAsync(ctx->pool.p, ctx->keep_pool.p, (size_t)ctx->pool_c * (size_t)(G + 2) * 8,
+                                  hipMemcpyDeviceToDevice, st));
     }
     HIPCHK(ctx->radix_tmp.ensure(std::max(radix_tmp_bytes(ctx->P + 1),
                                           chain_radix_tmp_bytes(std::min<uint64_t>(ctx->P, find_chunk()) + 1))));
@@ -709,6 +779,10 @@ int find_tail(mums_ctx* ctx, const MatchParams& mp, const uint32_t* packed, Rows
     ctx->emit_tbl = ctx->tbl.as<uint32_t>();
     ctx->emit_base = ctx->bstart.as<uint32_t>();
     if (ctx->P == 0) HIPCHK(hipEventRecord(ctx->ev[EV_CHAINS], st));
+    if (ctx->P == 0 && carried) {   // no AddHashEntry call: the table stays as it was kept
+        const int rc = find_replay_dispatch(ctx, MatProbes{}, mp, st);
+        if (rc) return rc;
+    }
     if (ctx->P > 0) {
         MatProbes v{};
         // the seed stage's own probes, one pass: rows plus line keys and first starts
@@ -790,6 +864,15 @@ int find_tail(mums_ctx* ctx, const MatchParams& mp, const uint32_t* packed, Rows
         if (rc) return rc;
     }
     ctx->stage_done = MUMS_STAGE_ALL;
+    // the result is the hash table (MemHash.cpp:126): a kept table is consumed by this find,
+    // and mums_clear_sequences can take the next one from this list and tsize
+    ctx->keep_on = false;
+    ctx->table_fresh = true;
+    ctx->fresh_M = ctx->M;
+    ctx->fresh_G = G;
+    ctx->fresh_T = Tb;
+    ctx->fresh_coll = ctx->hc.collisions + ctx->carry_coll;
+    ctx->list_edited = false;
     return MUMS_OK;
 }
 
@@ -1064,7 +1147,7 @@ void fill_stats(mums_ctx* ctx, uint64_t n) {
     s.chunks = ctx->nchunks;
     if (ctx->stage_done >= MUMS_STAGE_ALL) {
         s.mem_count = ctx->pcompat ? ctx->M : ctx->hc.entries;   // compat: entries of the merged table
-        s.collision_count = ctx->hc.collisions;
+        s.collision_count = ctx->hc.collisions + ctx->carry_coll;   // cumulative over a kept table's finds
         s.ms_chains = el(EV_BUCKETS, EV_CHAINS);
         s.ms_replay = el(EV_CHAINS, EV_REPLAY);
         s.chains = ctx->hc.nchains;
@@ -1469,6 +1552,7 @@ int prepare_run(mums_ctx* ctx, const std::vector<uint64_t>& lens) {
     ctx->offset_log.clear();
     ctx->log_host = false;
     ctx->M = ctx->P = 0;
+    ctx->carry_coll = 0;
     const int G = (int)lens.size();
     uint64_t total = 0;
     for (uint64_t n : lens) total += n;
@@ -2165,7 +2249,7 @@ int mums_ctx_destroy(mums_ctx* ctx) {
                       &ctx->logA, &ctx->logB, &ctx->logvA, &ctx->logvB, &ctx->tiebuf, &ctx->fk, &ctx->fkloc,
                       &ctx->crbuf, &ctx->crcnt, &ctx->crlive, &ctx->crruns, &ctx->crall, &ctx->fsk, &ctx->bst2,
                       &ctx->side, &ctx->bst8, &ctx->cbst, &ctx->dsarr, &ctx->labx, &ctx->rkpool0, &ctx->rkpool1,
-                      &ctx->rku32, &ctx->ascii_all};
+                      &ctx->rku32, &ctx->ascii_all, &ctx->keep_pool, &ctx->keep_cnt};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i < EV_COUNT; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
@@ -2198,6 +2282,11 @@ int mums_set_params(mums_ctx* ctx, uint32_t repeat_tol, uint32_t enum_tol, uint3
     if (check_ctx(ctx)) return MUMS_E_INVALID;
     if (table_size == 0 || table_size > 0x80000000u)
         return fail(ctx, MUMS_E_INVALID, "table size must be in [1, 2^31]");
+    if (ctx->keep_on && ctx->keep_n > 0 && table_size != ctx->keep_T)   // SetTableSize empties the table
+        return fail(ctx, MUMS_E_INVALID, "table size differs from the table kept by ClearSequences (mums_clear drops it)");
+    // a finished find's table that ClearSequences has not taken yet: MemHash::SetTableSize
+    // (MemHash.cpp:95-102) empties it; the result list stays readable
+    if (ctx->table_fresh && table_size != ctx->fresh_T) ctx->table_fresh = false;
     ctx->repeat_tol = repeat_tol;
     ctx->enum_tol = enum_tol;
     ctx->table_size = table_size;
@@ -2253,6 +2342,52 @@ int mums_clear(mums_ctx* ctx) {
     ctx->stage_done = 0;
     ctx->M = ctx->P = ctx->N = 0;
     ctx->st = mums_stats{};
+    ctx->keep_on = ctx->table_fresh = ctx->list_edited = false;
+    ctx->keep_n = ctx->keep_coll = ctx->carry_coll = 0;
+    ctx->pool_c = 0;
+    return MUMS_OK;
+}
+
+// MemHash::ClearSequences (MemHash.cpp:71-74) = MatchFinder::Clear only: the genomes go, the
+// hash table (mem_table, mem_table_count, m_mem_count, m_collision_count) stays for the next find
+int mums_clear_sequences(mums_ctx* ctx) {
+    if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (ctx->shard) return fail(ctx, MUMS_E_UNSUPPORTED, "ClearSequences on a sharded context");
+    HIPCHK(hipSetDevice(ctx->device));
+    if (ctx->table_fresh) {   // a completed find since the last Clear / ClearSequences: its table is kept
+        if (ctx->list_edited)
+            return fail(ctx, MUMS_E_INVALID, "ClearSequences: the context's MatchList was filtered or replaced since "
+                                             "FindMatches, it is no longer the hash table");
+        if (ctx->fresh_M >= 0xFFFFFFF0ull)
+            return fail(ctx, MUMS_E_UNSUPPORTED, "ClearSequences: more than 2^32 entries in the table");
+        // the find's own sequence count and table size: gt and table_size may have changed since
+        const uint64_t M = ctx->fresh_M;
+        const int G = ctx->fresh_G;
+        const uint32_t T = ctx->fresh_T;
+        hipStream_t st = ctx->stream;
+        if (M > 0) {
+            HIPCHK(ctx->keep_pool.ensure((M + 1) * (size_t)(G + 2) * 8));
+            HIPCHK(ctx->keep_cnt.ensure((size_t)T * 4 + 64));
+            HIPCHK(launch_keep_pack(ctx->out_len.as<uint64_t>(), ctx->out_s.as<int64_t>(), M, G,
+                                    ctx->keep_pool.as<int64_t>(), st));
+            HIPCHK(hipMemcpyAsync(ctx->keep_cnt.p, ctx->tsize.p, (size_t)T * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        ctx->keep_n = M;
+        ctx->keep_G = G;
+        ctx->keep_T = T;
+        ctx->keep_coll = ctx->fresh_coll;
+        ctx->table_fresh = false;
+    } else if (!ctx->keep_on) {   // nothing hashed yet (ProgressiveAligner.cpp:642): an empty table
+        ctx->keep_n = 0;
+        ctx->keep_coll = 0;
+    }
+    ctx->keep_on = true;
+    for (auto& g : ctx->genomes)
+        if (g.owned && g.d_ptr) (void)hipFree((void*)g.d_ptr);
+    ctx->genomes.clear();
+    ctx->stage_done = 0;
+    ctx->M = ctx->P = ctx->N = 0;
     return MUMS_OK;
 }
 
@@ -2265,12 +2400,15 @@ int mums_find_stage(mums_ctx* ctx, int stage) {
     for (auto& g : ctx->genomes) lens.push_back(g.n);
     int rc = prepare_run(ctx, lens);
     if (rc) return rc;
+    const bool big = ctx->N >= 0xFFFFFFF0ull || getenv("MUMS_DEV_CHUNK_RECORDS") != nullptr;
+    if (stage >= MUMS_STAGE_ALL && ctx->keep_on && ctx->keep_n > 0 &&
+        (rc = carried_refusal(ctx, big, false)) != MUMS_OK)
+        return rc;
     if (ctx->genomes.empty()) {
         ctx->stage_done = MUMS_STAGE_ALL;
         ctx->st = mums_stats{};
         return MUMS_OK;
     }
-    const bool big = ctx->N >= 0xFFFFFFF0ull || getenv("MUMS_DEV_CHUNK_RECORDS") != nullptr;
     if (big && ctx->pcompat)
         return fail(ctx, MUMS_E_UNSUPPORTED, "more than 2^32 seed-mers: ParallelMemHash compat not supported");
     if (ctx->pcompat && ctx->pairwise && ctx->enum_tol > 1)   // (no reference class combines the two)
@@ -2352,6 +2490,16 @@ int mums_result_copy(mums_ctx* ctx, uint64_t* lengths, int64_t* starts) {
 
 int mums_mem_table_count(mums_ctx* ctx, uint32_t* counts, uint32_t table_size) {
     if (check_ctx(ctx) || !counts) return MUMS_E_INVALID;
+    if (ctx->stage_done < MUMS_STAGE_ALL && ctx->keep_on) {   // after ClearSequences: the kept table's counts
+        if (ctx->keep_n == 0) {
+            std::fill(counts, counts + table_size, 0u);
+            return MUMS_OK;
+        }
+        if (table_size != ctx->keep_T) return fail(ctx, MUMS_E_INVALID, "table_size differs from the kept table's");
+        HIPCHK(hipSetDevice(ctx->device));
+        HIPCHK(hipMemcpy(counts, ctx->keep_cnt.p, (size_t)table_size * 4, hipMemcpyDeviceToHost));
+        return MUMS_OK;
+    }
     if (ctx->stage_done < MUMS_STAGE_ALL) return fail(ctx, MUMS_E_INVALID, "no completed FindMatches on this context");
     if (table_size != ctx->table_size) return fail(ctx, MUMS_E_INVALID, "table_size differs from the context's");
     HIPCHK(hipSetDevice(ctx->device));
@@ -2618,6 +2766,7 @@ int match_filter(mums_ctx* ctx, uint32_t mult, uint64_t min_len) {
     HIPCHK(hipStreamSynchronize(st));
     std::swap(ctx->out_len, ctx->flen);
     std::swap(ctx->out_s, ctx->fs);
+    ctx->list_edited = true;
     ctx->M = kept;
     return MUMS_OK;
 }
@@ -2934,6 +3083,7 @@ int mums_eliminate_overlaps(mums_ctx* ctx) {
     HIPCHK(eo_gather(ctx->eo, G, ctx->flen.as<uint64_t>(), ctx->fs.as<int64_t>(), ctx->stream));
     std::swap(ctx->out_len, ctx->flen);
     std::swap(ctx->out_s, ctx->fs);
+    ctx->list_edited = true;
     ctx->M = n;
     return MUMS_OK;
 }
@@ -2963,6 +3113,7 @@ int mums_eliminate_overlaps_v2(mums_ctx* ctx, const uint32_t* seq_ids, uint32_t 
     HIPCHK(eo_gather(ctx->eo, G, ctx->flen.as<uint64_t>(), ctx->fs.as<int64_t>(), ctx->stream));
     std::swap(ctx->out_len, ctx->flen);
     std::swap(ctx->out_s, ctx->fs);
+    ctx->list_edited = true;
     ctx->M = n;
     return MUMS_OK;
 }
@@ -2984,6 +3135,7 @@ int mums_load_matches(mums_ctx* ctx, uint32_t seq_count, uint64_t count, const u
     ctx->gt.G = (int)seq_count;
     ctx->M = count;
     ctx->P = 0;
+    ctx->list_edited = true;
     ctx->stage_done = MUMS_STAGE_ALL;
     return MUMS_OK;
 }

@@ -385,6 +385,17 @@ hipError_t launch_replay_kept(View v, const GenomeTable& gt, const MatchParams& 
                               void* ctr, uint64_t* dbg, hipStream_t st, uint64_t* mlog, uint32_t** tbl_out,
                               const uint32_t** base_out, void* (*alloc)(void*, size_t), void* alloc_ctx,
                               const uint32_t* jl = nullptr);
+// FindMatches onto a kept table (MemHash::ClearSequences): pool = C carried entries (kcnt[b]
+// per bucket, bucket-major in vector order) followed by the nch new chain entries; jl = chain /
+// probe per line position (launch_chains).  Every probe runs AddHashEntry's exact search.
+template <int MG, typename View>
+hipError_t launch_replay_carried(View v, const GenomeTable& gt, const MatchParams& mp, int L, uint64_t P,
+                                 const int64_t* pool, uint32_t C, const uint32_t* kcnt, uint32_t nch,
+                                 const uint32_t* jl, uint32_t lds_max, uint32_t* tsize, void* ctr, hipStream_t st,
+                                 uint64_t* mlog, uint32_t** tbl_out, const uint32_t** base_out,
+                                 void* (*alloc)(void*, size_t), void* alloc_ctx);
+// a finished find's MatchList (bucket-major) as pool entries {length, offset, starts}
+hipError_t launch_keep_pack(const uint64_t* len, const int64_t* s, uint64_t M, int G, int64_t* pool, hipStream_t st);
 // chains.hip: chain labelling of the probes (key order) before the replay
 // context accessors for the multi-GPU orchestration (shard_comm.hip; mums_capi.hip)
 }  // namespace mums

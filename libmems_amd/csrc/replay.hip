@@ -1748,6 +1748,308 @@ hipError_t launch_replay_kept(View v, const GenomeTable& gt, const MatchParams& 
                                  Kc, scr, d_scan_tmp, lds_cap, tsize, ctr, dbg, st, mlog);
 }
 
+// ---- the replay onto a kept table (MemHash::ClearSequences) -------------
+// After ClearSequences (MemHash.cpp:71-74) the hash table survives, so the next FindMatches
+// runs every AddHashEntry against buckets that already hold the earlier finds' entries.  The
+// pool of such a find is the C carried entries (bucket-major, each bucket in its vector order)
+// followed by the new chain entries; a bucket's vector starts as its carried slots.  None of
+// the shortcuts above holds against carried entries (one may contain a chain-first probe, push
+// lower_bound past a chain's own entry, or sit out of rank order), so every probe of the find
+// is kept and runs AddHashEntry's exact search (round_first) in key order.
+
+// the vector slot of pool entry id
+template <int MG>
+__device__ __forceinline__ uint4 entry_slot(const int64_t* __restrict__ pool, uint32_t id, int G,
+                                            const uint32_t* __restrict__ bkey) {
+    const int64_t* e = pool + (uint64_t)id * (uint64_t)(G + 2);
+    uint32_t m = 0;
+    int64_t s0 = 0;
+    for (int g = G - 1; g >= 0; --g) {
+        const int64_t sg = e[2 + g];
+        if (sg != 0) { m |= g < 32 ? 1u << g : 0u; s0 = sg; }
+    }
+    uint32_t key;
+    if constexpr (MG > 32) key = bkey[id];
+    else key = __builtin_bitreverse32(m);
+    return make_uint4(id, key, (uint32_t)s0, (uint32_t)e[0]);
+}
+
+// key[j] = bucket << 32 | probe (key order index) of line position j; val[j] = j
+__global__ __launch_bounds__(kBlock) void carried_keys_kernel(const uint32_t* __restrict__ jl, uint64_t P,
+                                                              const int64_t* __restrict__ pool_new, int G,
+                                                              uint32_t table_size, double inv_t,
+                                                              uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
+    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= P) return;
+    const int64_t off = pool_new[(uint64_t)jl[j] * (uint64_t)(G + 2) + 1];
+    key[j] = ((uint64_t)bucket_of_fast(off, table_size, inv_t) << 32) | jl[P + j];
+    val[j] = (uint32_t)j;
+}
+
+// summaries of all probes in (bucket, key order): every one runs the exact search (bit 30)
+template <int MG, typename View>
+__global__ __launch_bounds__(kBlock) void carried_summary_kernel(View v, GenomeTable gt, int L,
+                                                                 const uint64_t* __restrict__ skey, uint64_t P,
+                                                                 const uint32_t* __restrict__ sj,
+                                                                 const uint32_t* __restrict__ jl, uint32_t C,
+                                                                 const int64_t* __restrict__ pool,
+                                                                 const uint32_t* __restrict__ bkey,
+                                                                 uint4* __restrict__ summ, uint4* __restrict__ summ_b) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= P) return;
+    const uint32_t k = (uint32_t)skey[i];
+    Mhe<MG> Q;
+    load_probe<MG>(v, k, gt.G, L, Q);
+    const uint4 es = entry_slot<MG>(pool, C + jl[sj[i]], gt.G, bkey);   // same presence mask as the probe
+    summ[i] = make_uint4(es.y, (uint32_t)start_at(Q, first_start(Q)), es.x, 0x40000000u);
+    summ_b[i] = make_uint4(es.z, es.w, 0u, k);
+}
+
+// cap[b] = carried entries + probes of bucket b: the most its vector can hold
+__global__ __launch_bounds__(kBlock) void carried_cap_kernel(const uint32_t* __restrict__ kcnt,
+                                                             const uint32_t* __restrict__ cbeg,
+                                                             const uint32_t* __restrict__ cend, uint32_t T,
+                                                             uint32_t* __restrict__ cap) {
+    const uint32_t b = blockIdx.x * kBlock + threadIdx.x;
+    if (b < T) cap[b] = kcnt[b] + (cend[b] - cbeg[b]);
+}
+
+// One workgroup per bucket with vmin < carried + probes <= vmax: the vector starts as the
+// bucket's carried slots (in LDS, or in its global slice of vcap[b] slots when they outnumber
+// lds_cap), then the rounds of replay_kernel with every probe on the exact search.
+template <int MG, int RB, typename View>
+__global__ __launch_bounds__(RB) void replay_carried_kernel(
+    View v, GenomeTable gt, MatchParams mp, int L, const uint4* __restrict__ summ, const uint4* __restrict__ summ_b,
+    const uint32_t* __restrict__ cbeg, const uint32_t* __restrict__ cend, const uint32_t* __restrict__ kcnt,
+    const uint32_t* __restrict__ kbase, const uint32_t* __restrict__ vbase, const uint32_t* __restrict__ bkey,
+    uint32_t* __restrict__ tbl, uint4* __restrict__ spill, const int64_t* __restrict__ pool, uint32_t lds_cap,
+    uint32_t* __restrict__ tsize, DevCounters* ctr, uint32_t vmin, uint32_t vmax, uint64_t* __restrict__ mlog) {
+    extern __shared__ uint4 s_tab[];
+    __shared__ int red[RB / 64];
+    __shared__ uint32_t s_ins;
+    __shared__ uint4 s_new;
+    const uint32_t tid = threadIdx.x, b = blockIdx.x;
+    const uint32_t beg = cbeg[b], K_b = cend[b] - beg, nc = kcnt[b];
+    const uint32_t vcap = nc + K_b;
+    if (vcap == 0 || vcap <= vmin || vcap > vmax) return;
+    const uint32_t ob = vbase[b], kb0 = kbase[b];
+    const int G = gt.G;
+    bool in_lds = nc <= lds_cap;
+    for (uint32_t i = tid; i < nc; i += RB) {
+        const uint4 s = entry_slot<MG>(pool, kb0 + i, G, bkey);
+        if (in_lds) s_tab[i] = s;
+        else spill[ob + i] = s;
+    }
+    __syncthreads();
+    uint32_t t = nc;
+    unsigned long long coll = 0;
+    for (uint32_t w0 = 0; w0 < K_b; w0 += RB) {
+        const uint32_t c = min((uint32_t)RB, K_b - w0);
+        const uint4 me = tid < c ? summ[beg + w0 + tid] : make_uint4(0, 0, 0, 0);
+        const uint4 mb = tid < c ? summ_b[beg + w0 + tid] : make_uint4(0, 0, 0, 0);
+        uint32_t done = 0;
+        while (done < c) {
+            const int first = in_lds
+                ? round_first<MG, RB, View>(s_tab, t, done, c, me, mb, v, gt, mp, L, nullptr, pool, red)
+                : round_first<MG, RB, View>(spill + ob, t, done, c, me, mb, v, gt, mp, L, nullptr, pool, red);
+            if (first == RB) {
+                coll += c - done;
+                break;
+            }
+            coll += (unsigned long long)(first - (int)done);
+            if ((int)tid == first) {
+                s_ins = in_lds ? insert_pos<MG>(s_tab, t, me.z, me.x, (int64_t)mb.x, (int64_t)mb.y, pool, G)
+                               : insert_pos<MG>(spill + ob, t, me.z, me.x, (int64_t)mb.x, (int64_t)mb.y, pool, G);
+                s_new = make_uint4(me.z, me.x, mb.x, mb.y);
+                log_insert(mlog, ctr, mb.w, me.z);
+            }
+            if (in_lds && t + 1 > lds_cap) {   // spill the vector to the bucket's global slice
+                for (uint32_t k = tid; k < t; k += RB) spill[ob + k] = s_tab[k];
+                in_lds = false;
+            }
+            __syncthreads();
+            if (in_lds) shift_insert<RB>(s_tab, t, s_ins, s_new);
+            else shift_insert<RB>(spill + ob, t, s_ins, s_new);
+            t += 1;   // <= vcap: every probe inserts at most once
+            done = (uint32_t)first + 1;
+        }
+    }
+    if (in_lds)
+        for (uint32_t k = tid; k < t; k += RB) tbl[ob + k] = s_tab[k].x;
+    else
+        for (uint32_t k = tid; k < t; k += RB) tbl[ob + k] = spill[ob + k].x;
+    if (tid == 0) {
+        tsize[b] = t;
+        atomicAdd(&ctr->collisions, coll);
+        atomicAdd(&ctr->entries, (unsigned long long)t);
+    }
+}
+
+// the kept table from a finished find's MatchList (bucket-major): pool entries {length,
+// CalculateOffset (MatchHashEntry.cpp:141-160; an extended entry's equals its probe's), starts}
+__global__ __launch_bounds__(kBlock) void keep_pack_kernel(const uint64_t* __restrict__ len,
+                                                           const int64_t* __restrict__ s, uint64_t M, int G,
+                                                           int64_t* __restrict__ pool) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= M) return;
+    const int64_t* r = s + i * (uint64_t)G;
+    int64_t* e = pool + i * (uint64_t)(G + 2);
+    const int64_t l = (int64_t)len[i];
+    int ref = -1;
+    int64_t sref = 0, off = 0;
+    for (int g = 0; g < G; ++g) {
+        const int64_t x = r[g];
+        e[2 + g] = x;
+        if (x == 0) continue;
+        if (ref < 0) { ref = g; sref = x; }
+        else off += x - sref - (x < 0 ? l : 0);
+    }
+    e[0] = l;
+    e[1] = off;
+}
+
+hipError_t launch_keep_pack(const uint64_t* len, const int64_t* s, uint64_t M, int G, int64_t* pool, hipStream_t st) {
+    if (M == 0) return hipSuccess;
+    hipLaunchKernelGGL(keep_pack_kernel, dim3((unsigned)((M + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, len, s, M,
+                       G, pool);
+    return hipGetLastError();
+}
+
+// FindMatches onto a kept table: pool = C carried entries (kcnt[b] per bucket, bucket-major in
+// vector order) then the nch new chain entries; jl = chain / probe per line position
+// (launch_chains).  Every buffer is sized here from C + P (the most entries the table can
+// end with); the bucket vectors come back in *tbl_out at bases *base_out.
+template <int MG, typename View>
+hipError_t launch_replay_carried(View v, const GenomeTable& gt, const MatchParams& mp, int L, uint64_t P,
+                                 const int64_t* pool, uint32_t C, const uint32_t* kcnt, uint32_t nch,
+                                 const uint32_t* jl, uint32_t lds_max, uint32_t* tsize, void* ctr, hipStream_t st,
+                                 uint64_t* mlog, uint32_t** tbl_out, const uint32_t** base_out,
+                                 void* (*alloc)(void*, size_t), void* alloc_ctx) {
+    const uint32_t Tb = mp.table_size;
+    const int G = gt.G;
+    const uint64_t V = (uint64_t)C + P;   // vector slots over all buckets
+    if (V >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
+    const uint64_t P1 = P + 1, T1 = (uint64_t)Tb + 32, NB = (uint64_t)C + nch + 1;
+    const size_t rtmp = std::max(radix_tmp_bytes(P1), radix_tmp_bytes(NB));
+    const size_t stmp = std::max(scan_tmp_bytes(T1), scan_tmp_bytes(NB));
+    const bool dense = G > 32;
+    const size_t need = P1 * (8 * 3 + 4 * 3 + 16 * 2) + (V + 1) * (16 + 4) + T1 * 4 * 5 + rtmp + stmp +
+                        (dense ? NB * (8 * 3 + 4 * 4) : 0) + 40 * 256;
+    char* p = (char*)alloc(alloc_ctx, need);
+    if (!p) return hipErrorOutOfMemory;
+    auto carve = [&](size_t bytes) {
+        char* r = p;
+        p += (bytes + 255) & ~(size_t)255;
+        return (void*)r;
+    };
+    uint64_t* kA = (uint64_t*)carve(P1 * 8);
+    uint64_t* kB = (uint64_t*)carve(P1 * 8);
+    uint32_t* vA = (uint32_t*)carve(P1 * 4);
+    uint32_t* vB = (uint32_t*)carve(P1 * 4);
+    uint64_t* kC = (uint64_t*)carve(P1 * 8);
+    uint32_t* vC = (uint32_t*)carve(P1 * 4);
+    uint4* summ = (uint4*)carve(P1 * 16);
+    uint4* summ_b = (uint4*)carve(P1 * 16);
+    uint4* spill = (uint4*)carve((V + 1) * 16);
+    uint32_t* tbl = (uint32_t*)carve((V + 1) * 4);
+    uint32_t* cbeg = (uint32_t*)carve(T1 * 4);
+    uint32_t* cend = (uint32_t*)carve(T1 * 4);
+    uint32_t* kbase = (uint32_t*)carve(T1 * 4);
+    uint32_t* vbase = (uint32_t*)carve(T1 * 4);
+    uint32_t* vcap = (uint32_t*)carve(T1 * 4);
+    void* rt = carve(rtmp);
+    void* sc = carve(stmp);
+    *tbl_out = tbl;
+    *base_out = vbase;
+    hipError_t e = hipSuccess;
+    const uint32_t* bkey = nullptr;
+    if (dense) {   // dense block ranks over the carried and the new entries' masks together
+        uint64_t* bm = (uint64_t*)carve(NB * 8);
+        uint64_t* bA = (uint64_t*)carve(NB * 8);
+        uint64_t* bB = (uint64_t*)carve(NB * 8);
+        uint32_t* wA = (uint32_t*)carve(NB * 4);
+        uint32_t* wB = (uint32_t*)carve(NB * 4);
+        uint32_t* step = (uint32_t*)carve(NB * 4);
+        uint32_t* bk = (uint32_t*)carve(NB * 4);
+        bkey = block_keys(pool, C + nch, G, bm, bA, wA, bB, wB, step, bk, rt, sc, st, &e);
+        if (e != hipSuccess) return e;
+    }
+    if ((e = hipMemsetAsync(cbeg, 0, T1 * 4, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(cend, 0, T1 * 4, st)) != hipSuccess) return e;
+    if (P > 0) {
+        int tbits = 1;
+        while (tbits < 32 && ((uint64_t)1 << tbits) < (uint64_t)Tb) ++tbits;
+        const unsigned pgrid = (unsigned)((P + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(carried_keys_kernel, dim3(pgrid), dim3(kBlock), 0, st, jl, P,
+                           pool + (uint64_t)C * (uint64_t)(G + 2), G, Tb, 1.0 / (double)Tb, kA, vA);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        const uint64_t* skey = kA;
+        const uint32_t* sj = vA;
+        if (P > 1) {
+            int b3 = 0;
+            if ((e = radix_sort<uint64_t>(kA, vA, P, 32 + tbits, kB, vB, kC, vC, rt, &b3, st)) != hipSuccess) return e;
+            skey = b3 ? kC : kB;
+            sj = b3 ? vC : vB;
+        }
+        hipLaunchKernelGGL((carried_summary_kernel<MG, View>), dim3(pgrid), dim3(kBlock), 0, st, v, gt, L, skey, P, sj,
+                           jl, C, pool, bkey, summ, summ_b);
+        hipLaunchKernelGGL(kept_ranges_kernel, dim3(pgrid), dim3(kBlock), 0, st, skey, (uint32_t)P, cbeg, cend, P,
+                           (DevCounters*)ctr);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    const unsigned tgrid = (Tb + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(carried_cap_kernel, dim3(tgrid), dim3(kBlock), 0, st, kcnt, (const uint32_t*)cbeg,
+                       (const uint32_t*)cend, Tb, vcap);
+    if ((e = hipMemcpyAsync(vbase, vcap, (size_t)Tb * 4, hipMemcpyDeviceToDevice, st)) != hipSuccess) return e;
+    if ((e = exclusive_scan_u32(vbase, Tb, sc, nullptr, st)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(kbase, kcnt, (size_t)Tb * 4, hipMemcpyDeviceToDevice, st)) != hipSuccess) return e;
+    if ((e = exclusive_scan_u32(kbase, Tb, sc, nullptr, st)) != hipSuccess) return e;
+    // capacities, checked on the host before anything writes a vector: the slices must tile
+    // [0, C + P) and the carried counts must sum to C
+    std::vector<uint32_t> hcap(Tb), hcnt(Tb);
+    if ((e = hipMemcpyAsync(hcap.data(), vcap, (size_t)Tb * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(hcnt.data(), kcnt, (size_t)Tb * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+    uint64_t sum_cap = 0, sum_cnt = 0;
+    uint32_t vmax = 0;
+    for (uint32_t b = 0; b < Tb; ++b) {
+        sum_cap += hcap[b];
+        sum_cnt += hcnt[b];
+        vmax = std::max(vmax, hcap[b]);
+    }
+    if (sum_cap != V || sum_cnt != C) return hipErrorInvalidValue;
+    constexpr uint32_t kSmall = 64;
+    hipLaunchKernelGGL((replay_carried_kernel<MG, 64, View>), dim3(Tb), dim3(64), kSmall * sizeof(uint4), st, v, gt, mp,
+                       L, (const uint4*)summ, (const uint4*)summ_b, (const uint32_t*)cbeg, (const uint32_t*)cend, kcnt,
+                       (const uint32_t*)kbase, (const uint32_t*)vbase, bkey, tbl, spill, pool, kSmall, tsize,
+                       (DevCounters*)ctr, 0u, kSmall, mlog);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (vmax <= kSmall) return hipSuccess;
+    constexpr int RB = replay_block<MG>();
+    const uint32_t lds_cap = std::max<uint32_t>(kSmall, std::min(vmax, lds_max));
+    const size_t lds = (size_t)lds_cap * sizeof(uint4);
+    e = hipFuncSetAttribute((const void*)replay_carried_kernel<MG, RB, View>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((replay_carried_kernel<MG, RB, View>), dim3(Tb), dim3(RB), lds, st, v, gt, mp, L,
+                       (const uint4*)summ, (const uint4*)summ_b, (const uint32_t*)cbeg, (const uint32_t*)cend, kcnt,
+                       (const uint32_t*)kbase, (const uint32_t*)vbase, bkey, tbl, spill, pool, lds_cap, tsize,
+                       (DevCounters*)ctr, kSmall, 0xFFFFFFFFu, mlog);
+    return hipGetLastError();
+}
+
+#define MUMS_INST_REPLAY_CARRIED(MG, V)                                                                          \
+    template hipError_t launch_replay_carried<MG, V>(V, const GenomeTable&, const MatchParams&, int, uint64_t,       \
+                                                     const int64_t*, uint32_t, const uint32_t*, uint32_t,            \
+                                                     const uint32_t*, uint32_t, uint32_t*, void*, hipStream_t,       \
+                                                     uint64_t*, uint32_t**, const uint32_t**,                        \
+                                                     void* (*)(void*, size_t), void*);
+MUMS_INST_REPLAY_CARRIED(4, MatProbes)
+MUMS_INST_REPLAY_CARRIED(8, MatProbes)
+MUMS_INST_REPLAY_CARRIED(16, MatProbes)
+MUMS_INST_REPLAY_CARRIED(32, MatProbes)
+MUMS_INST_REPLAY_CARRIED(64, MatProbes)
+
 // ---- the sharded kept-probe export -------------------------------
 // The bucket owner receives every rank's chain entries (source-rank order; a chain whose probes
 // sit on several ranks arrives once per rank), merges equal ones (launch_chain_merge) and

@@ -7,6 +7,8 @@
 //   mums_find sml G n weight p [mask]        the drop-in path of Aligner.cpp:1181-1184 /
 //       CreateMemorySMLs (MatchList.h:409-435): HipSML::Create per genome (deferred), then
 //       MemHash::FindMatches from ml.sml_table; stderr reports the SMLs materialised (0)
+//   mums_find family G n weight p            progressiveMauve's seed family: Clear, then seed ranks
+//       0-2 each ClearSequences + FindMatches on one MemHash (ProgressiveAligner.cpp:619-653)
 //   mums_find smldump G n weight p g stride  genome g's deferred SML read back: every entry
 //       (position, mer) through operator[], then FindMer of every stride-th entry's mer
 #include <unistd.h>
@@ -124,6 +126,38 @@ int main(int argc, char** argv) {
                       << std::chrono::duration<double, std::milli>(t1 - t0).count() << " find ms "
                       << std::chrono::duration<double, std::milli>(t2 - t1).count() << " materialized "
                       << mums::HipSML::Materializations() << "\n";
+        } catch (const std::exception& e) {
+            std::cerr << "error: " << e.what() << "\n";
+            return 1;
+        }
+        return 0;
+    }
+    if (mode == "family" && argc >= 6) {
+        // pairwiseAnchorSearch's seed-family loop (ProgressiveAligner.cpp:619-653): Clear, then per
+        // seed rank ClearSequences + FindMatches on the one MemHash; the MatchList is the whole table
+        const int G = atoi(argv[2]);
+        const uint64_t n = strtoull(argv[3], nullptr, 10);
+        const int weight = atoi(argv[4]);
+        const double p = atof(argv[5]);
+        try {
+            const std::vector<std::string> seq_table = generate(G, n, p, 12345);
+            mums::MemHash gap_mh(0);
+            mums::MatchList ml;
+            gap_mh.Clear();
+            for (int seed_rank = 0; seed_rank < 3; ++seed_rank) {
+                gap_mh.ClearSequences();
+                gap_mh.SetSeed((uint64_t)mums_get_seed(weight, seed_rank));
+                ml.clear();
+                ml.seq_table = seq_table;
+                gap_mh.FindMatches(ml);
+            }
+            ml.clear();
+            gap_mh.GetMatchList(ml);
+            std::ostringstream os;
+            for (const auto& m : ml) os << m << '\n';
+            std::cout << os.str();
+            std::cerr << "matches " << ml.size() << " mems " << gap_mh.MemCount() << " collisions "
+                      << gap_mh.MemCollisionCount() << "\n";
         } catch (const std::exception& e) {
             std::cerr << "error: " << e.what() << "\n";
             return 1;
