@@ -3,7 +3,8 @@ every round, what tests/seed_family_model.c (the oracle's MemHash looped over th
 one table) gives -- count and md5 of the MatchList (lengths <u8, then starts <i8), MemCount,
 MemCollisionCount, the round's AddHashEntry calls, md5 of mem_table_count (<u4) and of the
 match log; and under "chain" the count and md5 of case 1's family list after
-tests/eo2_model.cpp and LengthFilter(MIN_ANCHOR_LENGTH + 3).  Run from the repository root:  python tests/golden/make_seed_family_golden.py"""
+tests/eo2_model.cpp and LengthFilter(MIN_ANCHOR_LENGTH + 3), under "chain_k1" the same of
+k1_spill_mid_replay's list after round 1.  Run from the repository root:  python tests/golden/make_seed_family_golden.py"""
 import json
 import os
 import sys
@@ -27,8 +28,12 @@ def main():
             cl, cs = sf.chain_of_model(eo2, eo2.load_model(), rounds[-1])
             chain = dict(count=int(len(cl)), md5=sf.list_md5(cl, cs), min_length=sf.CHAIN_MIN_LENGTH)
             print("chain", chain)
+        if name == sf.SPILL:
+            cl, cs = sf.chain_of_model(eo2, eo2.load_model(), rounds[1])
+            chain_k1 = dict(count=int(len(cl)), md5=sf.list_md5(cl, cs), min_length=sf.CHAIN_MIN_LENGTH)
+            print("chain_k1", chain_k1)
     with open(sf.FIXTURE, "w") as f:
-        json.dump(dict(cases=out, chain=chain), f, indent=1, sort_keys=True)
+        json.dump(dict(cases=out, chain=chain, chain_k1=chain_k1), f, indent=1, sort_keys=True)
         f.write("\n")
 
 

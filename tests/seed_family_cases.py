@@ -1,7 +1,9 @@
 """Seed families (ClearSequences keeps the MemHash table, ProgressiveAligner.cpp:619-653): the
 cases shared by test_seed_family_cpu.py, test_gpu_seed_family.py and
 golden/make_seed_family_golden.py, the loader of tests/seed_family_model.c and the digests the
-fixture golden/seed_family_cases.json records."""
+fixture golden/seed_family_cases.json records.  A case may take its sequences from a generator of
+tests/repeat_inputs.py (`gen`, the same sequences in every round) and may replace the sequences
+of single rounds by those of a function of this module (`seqs`)."""
 from __future__ import annotations
 
 import ctypes
@@ -13,6 +15,7 @@ import subprocess
 
 import numpy as np
 
+import repeat_inputs
 from oracle import oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,6 +26,10 @@ FIXTURE = os.path.join(ROOT, "tests", "golden", "seed_family_cases.json")
 # name -> G, n, p, w (seed weight), T (table size), ranks (seed ranks in round order); optional:
 #   mode: dict(masked=, seq_mask=, pairwise=, repeat_tol=, enum_tol=)
 #   alt: {round: (n, rng_seed)} -- that round runs on other sequences of the same G and p
+#   gen: (generator of repeat_inputs.py, its keywords) -- the sequences of every round (n and p unused)
+#   seqs: {round: name of a function of this module} -- that round runs on the sequences it returns
+# The k cases exist for the paths of replay_carried_kernel / launch_replay_carried they reach
+# (test_seed_family_cpu.py::test_cases_reach_the_carried_replays_paths holds them to it).
 CASES = {
     "c1_pairwise_anchor": dict(G=2, n=30000, p=0.05, w=11, T=40000, ranks=(0, 1, 2)),
     "c1_order_201": dict(G=2, n=30000, p=0.05, w=11, T=40000, ranks=(2, 0, 1)),
@@ -36,8 +43,23 @@ CASES = {
     "c7_rt1_et2": dict(G=3, n=20000, p=0.03, w=9, T=64, ranks=(0, 1, 2), mode=dict(repeat_tol=1, enum_tol=2)),
     "c8_other_sequences": dict(G=2, n=30000, p=0.05, w=11, T=40000, ranks=(0, 1, 2), alt={2: (25000, 777)}),
     "c9_five_rounds": dict(G=2, n=30000, p=0.05, w=11, T=40000, ranks=(0, 1, 2, 0, 1)),
+    "k1_spill_mid_replay": dict(G=2, n=40000, p=1.0, w=9, T=1, ranks=(0, 1, 2)),
+    "k2_lds_carried_T3": dict(G=2, n=40000, p=1.0, w=9, T=3, ranks=(0, 1, 2)),
+    "k3_small_edge_T300": dict(G=2, n=50000, p=1.0, w=9, T=300, ranks=(0, 1, 2)),
+    "k4_g6": dict(G=6, n=4000, p=0.05, w=9, T=64, ranks=(0, 1, 2)),
+    "k5_g12": dict(G=12, n=3000, p=0.05, w=9, T=64, ranks=(0, 1, 2)),
+    "k6_g24": dict(G=24, n=2000, p=0.05, w=9, T=40000, ranks=(0, 1, 2)),
+    "k7_g32": dict(G=32, n=2000, p=0.05, w=9, T=64, ranks=(0, 1, 2)),
+    "k8_g33": dict(G=33, n=2000, p=0.05, w=9, T=64, ranks=(0, 1, 2)),
+    "k9_w21": dict(G=2, n=30000, p=0.02, w=21, T=40000, ranks=(0, 1, 2)),
+    "k10_n_gapped": dict(G=3, w=9, T=64, ranks=(0, 1, 2),
+                         gen=("n_gapped", dict(G=3, n=20000, gaps=((5000, 1500),), p=0.02, seed=7, shift=40))),
+    "k11_high_copy": dict(G=3, w=11, T=40000, ranks=(0, 1, 2),
+                          gen=("high_copy", dict(G=3, n=15000, copies=600, unit=100, seed=11))),
+    "k12_one_probe": dict(G=2, n=30000, p=0.05, w=11, T=40000, ranks=(0, 1), seqs={1: "one_probe_pair"}),
 }
 FIRST = "c1_pairwise_anchor"
+SPILL = "k1_spill_mid_replay"   # its bucket outgrows the replay's LDS vector during round 1
 RNG_SEED = 12345
 
 _seq_cache = {}
@@ -50,15 +72,42 @@ def sequences(G, n, p, rng=RNG_SEED):
     return _seq_cache[key]
 
 
+def generated(gen, kw):
+    key = (gen, repr(sorted(kw.items())))
+    if key not in _seq_cache:
+        _seq_cache[key] = getattr(repeat_inputs, gen)(**kw)
+    return _seq_cache[key]
+
+
+def one_probe_pair(run=19):
+    """Two unrelated 300-bp sequences that share one run of `run` bases (the bases on either side
+    of it differ).  19 is the length of the w11 rank-1 seed pattern, found by a search on the
+    model: 18 gives no AddHashEntry call under that seed, 20 gives two, 19 exactly one
+    (test_cases_reach_the_carried_replays_paths asserts it on the model)."""
+    a = bytearray(oracle.generate(1, 300, 0.0, 5)[0])
+    b = bytearray(oracle.generate(1, 300, 0.0, 6)[0])
+    b[180:180 + run] = a[100:100 + run]
+    for ia, ib in ((99, 179), (100 + run, 180 + run)):
+        if b[ib] == a[ia]:
+            b[ib] = b"ACGT"[(b"ACGT".index(a[ia]) + 1) % 4]
+    return [bytes(a), bytes(b)]
+
+
 def rounds_of(case):
     """[(sequences, seed pattern, oracle.find_matches keywords)] of a case, in round order."""
     c = CASES[case] if isinstance(case, str) else case
     mode = dict(c.get("mode", {}))
     out = []
     for r, rank in enumerate(c["ranks"]):
-        n, rng = c.get("alt", {}).get(r, (c["n"], RNG_SEED))
-        out.append((sequences(c["G"], n, c["p"], rng), oracle.get_seed(c["w"], rank),
-                    dict(table_size=c["T"], **mode)))
+        if r in c.get("seqs", {}):
+            seqs = globals()[c["seqs"][r]]()
+        elif "gen" in c:
+            seqs = generated(*c["gen"])
+        else:
+            n, rng = c.get("alt", {}).get(r, (c["n"], RNG_SEED))
+            seqs = sequences(c["G"], n, c["p"], rng)
+        assert len(seqs) == c["G"]
+        out.append((seqs, oracle.get_seed(c["w"], rank), dict(table_size=c["T"], **mode)))
     return out
 
 
@@ -164,6 +213,6 @@ def fixture():
         return json.load(f)["cases"]
 
 
-def fixture_chain():
+def fixture_chain(key="chain"):
     with open(FIXTURE) as f:
-        return json.load(f)["chain"]
+        return json.load(f)[key]

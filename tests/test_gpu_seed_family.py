@@ -99,7 +99,7 @@ def run_case(lib, recorded, live, name, after_round=None):
 
 @pytest.mark.parametrize("name", list(sf.CASES))
 def test_family_rounds(gpu_lib, recorded, live, name):
-    """Cases 1-9 of the issue: every round of every case against the fixture and the live model."""
+    """Every round of every case against the fixture and the live model."""
     run_case(gpu_lib, recorded, live, name)
 
 
@@ -134,6 +134,108 @@ def test_full_anchor_chain(gpu_lib, live):
     rec = sf.fixture_chain()
     assert sf.CHAIN_MIN_LENGTH == rec["min_length"]
     assert dict(count=len(got), md5=sf.list_md5(got.lengths, got.starts)) == dict(count=rec["count"], md5=rec["md5"])
+
+
+# ---- the carried replay's paths (the k cases; test_seed_family_cpu.py holds each case to the path
+# it exists for) -------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["k7_g32", "k8_g33"])
+def test_mask_key_edge_buckets(gpu_lib, recorded, live, name):
+    """G = 32 (every bit of entry_slot's presence mask) and G = 33 (the first count on dense block
+    keys): after the last round every entry sits in its own bucket -- MemTableCount is the
+    bincount of the returned list's entry buckets -- and each bucket's slice of the list is the
+    model's, in the model's order.  The digests imply it; here a failure names the bucket."""
+    T = sf.CASES[name]["T"]
+    with make_finder(gpu_lib, name) as mh:
+        mh.Clear()
+        for seqs, seed, _ in sf.rounds_of(name):
+            mh.ClearSequences()
+            mh.SetSeed(seed)
+            mh.FindMatches(seqs)
+        got = gpu_round(mh)
+    buckets = sf.oracle.entry_buckets(got["lengths"], got["starts"], T)
+    counts = np.bincount(buckets, minlength=T)
+    for b in range(T):
+        assert got["table_counts"][b] == counts[b], f"bucket {b}"
+    assert np.all(np.diff(buckets) >= 0)   # the list is the table, bucket-major
+    if live is not None:
+        m = live(name)[-1]
+        ends = np.cumsum(counts)
+        for b in range(T):
+            sl = slice(int(ends[b] - counts[b]), int(ends[b]))
+            assert np.array_equal(got["lengths"][sl], m["lengths"][sl]) and \
+                np.array_equal(got["starts"][sl], m["starts"][sl]), f"bucket {b}"
+    assert sf.digest(got) == recorded[name][-1]
+
+
+def test_spill_in_mid_replay_reaches_the_anchor_chain(gpu_lib, recorded, live):
+    """k1: the one bucket holds 6625 entries when round 1 starts and 13084 when it ends, so its
+    vector leaves LDS between two inserts of one window.  The list after round 1 is the model's
+    (check_round), and EliminateOverlaps_v2 + LengthFilter on it equal tests/eo2_model.cpp on the
+    model's list: the spilled vector's ids made it into the table."""
+    rounds = sf.rounds_of(sf.SPILL)[:2]
+    with make_finder(gpu_lib, sf.SPILL) as mh:
+        mh.Clear()
+        for r, (seqs, seed, _) in enumerate(rounds):
+            mh.ClearSequences()
+            mh.SetSeed(seed)
+            mh.FindMatches(seqs)
+            check_round(gpu_round(mh), recorded[sf.SPILL][r], live(sf.SPILL)[r] if live else None, sf.CASES[sf.SPILL])
+        family = len(mh.GetMatchList())
+        mh.EliminateOverlaps_v2()
+        mh.LengthFilter(sf.CHAIN_MIN_LENGTH)
+        got = mh.GetMatchList()
+    assert 0 < len(got) < family
+    if live is not None:
+        el, es = sf.chain_of_model(eo2, eo2.load_model(), live(sf.SPILL)[1])
+        assert np.array_equal(got.lengths, el) and np.array_equal(got.starts, es)
+    rec = sf.fixture_chain("chain_k1")
+    assert sf.CHAIN_MIN_LENGTH == rec["min_length"]
+    assert dict(count=len(got), md5=sf.list_md5(got.lengths, got.starts)) == dict(count=rec["count"], md5=rec["md5"])
+
+
+def test_restart_round_after_a_refused_find(gpu_lib, recorded, oracle_mod):
+    """k10 (one MER_REPEAT_LIMIT restart per round): a find with the wrong genome count onto the
+    kept table is refused, the table stays, and round 1 onto it is the fixture's round 1."""
+    (s0, seed0, _), (s1, seed1, _) = sf.rounds_of("k10_n_gapped")[:2]
+    with make_finder(gpu_lib, "k10_n_gapped") as mh:
+        mh.Clear()
+        mh.ClearSequences()
+        mh.SetSeed(seed0)
+        mh.FindMatches(s0)
+        assert sf.digest(gpu_round(mh)) == recorded["k10_n_gapped"][0]
+        mh.ClearSequences()
+        mh.SetSeed(seed1)
+        with pytest.raises(gpu_lib.MumsError) as e:
+            mh.FindMatches(list(s1) + [s1[0]])
+        assert e.value.code == gpu_lib.MUMS_E_INVALID
+        mh.ClearSequences()
+        mh.SetSeed(seed1)
+        mh.FindMatches(s1)
+        assert mh.stats()["restarts"] == oracle_mod.find_matches(s1, seed1, table_size=sf.CASES["k10_n_gapped"]["T"])[2]["restarts"] >= 1
+        assert sf.digest(gpu_round(mh)) == recorded["k10_n_gapped"][1]
+
+
+def test_family_without_the_match_log(gpu_lib, recorded):
+    """k3 with SetMatchLog(False) (log_insert is a no-op then; every other test logs): the
+    list, the counters and the table counts of every round are the fixture's."""
+    name = "k3_small_edge_T300"
+    with make_finder(gpu_lib, name) as mh:
+        mh.SetMatchLog(False)
+        mh.Clear()
+        for r, (seqs, seed, _) in enumerate(sf.rounds_of(name)):
+            mh.ClearSequences()
+            mh.SetSeed(seed)
+            mh.FindMatches(seqs)
+            with pytest.raises(gpu_lib.MumsError):
+                mh.MatchLog()   # nothing was logged
+            ml, st = mh.GetMatchList(), mh.stats()
+            empty = (np.zeros(0, np.uint64), np.zeros((0, 2), np.int64))
+            d = sf.digest(dict(lengths=ml.lengths, starts=ml.starts, mem_count=st["mem_count"],
+                               collisions=st["collision_count"], probes=st["probes"],
+                               table_counts=mh.MemTableCount(), log=empty))
+            for k in ("count", "list_md5", "mem_count", "collisions", "probes", "table_md5"):
+                assert d[k] == recorded[name][r][k], (r, k)
 
 
 # ---- case 11: edges -------------------------------------------------------------------------

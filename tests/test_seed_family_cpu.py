@@ -60,6 +60,10 @@ def test_chain_fixture_equals_live_models(results):
     rec = sf.fixture_chain()
     assert rec == dict(count=int(len(cl)), md5=sf.list_md5(cl, cs), min_length=sf.CHAIN_MIN_LENGTH)
     assert 0 < len(cl) < len(results[sf.FIRST][-1]["lengths"])
+    # the spilled vector of k1 after round 1
+    cl, cs = sf.chain_of_model(eo2, eo2.load_model(), results[sf.SPILL][1])
+    assert sf.fixture_chain("chain_k1") == dict(count=int(len(cl)), md5=sf.list_md5(cl, cs), min_length=sf.CHAIN_MIN_LENGTH)
+    assert 0 < len(cl) < len(results[sf.SPILL][1]["lengths"])
 
 
 def test_counters_are_cumulative(results):
@@ -105,3 +109,118 @@ def test_spill_case_starts_above_the_lds_vector(results):
     src = open(os.path.join(sf.ROOT, "libmems_amd", "csrc", "mums_capi.hip")).read()
     cap = int(re.search(r"kReplayLdsIds\s*=\s*(\d+)", src).group(1))
     assert len(results["c4_one_bucket_spill"][0]["lengths"]) > cap
+
+
+# condition of the carried replay (replay_carried_kernel / launch_replay_carried) -> the case
+# that exists for it; test_cases_reach_the_carried_replays_paths holds each case to its condition
+PATHS = {
+    "spill in mid-replay": "k1_spill_mid_replay",
+    "vector starts in global memory": "c4_one_bucket_spill",
+    "v == kSmall": "k3_small_edge_T300",
+    "v == kSmall + 1": "k3_small_edge_T300",
+    "long LDS-resident vector": "k2_lds_carried_T3",
+    "K > 1024": "k2_lds_carried_T3",
+    "K > 512": "k4_g6",
+    "K > 256": "k5_g12",
+    "carried-only bucket": "k6_g24",
+    "new-only bucket": "c1_pairwise_anchor",
+    "G in 1..4": "c5_g4_diagonal",
+    "G in 5..8": "k4_g6",
+    "G in 9..16": "k5_g12",
+    "G in 17..32": "k6_g24",
+    "G in 33..64": "c6_g34_dense_blocks",
+    "G == 32": "k7_g32",
+    "G == 33": "k8_g33",
+    "one probe": "k12_one_probe",
+    "restarts": ("k10_n_gapped", "k11_high_copy"),
+}
+
+
+def carried_paths(results, cases, cap, small, lanes):
+    """condition -> set of the plain cases (no `mode`: oracle.seed_probes is a plain MemHash)
+    with a carried round that meets it.  Per bucket of a carried round: nc carried entries, K
+    probes, v = nc + K (what launch_replay_carried dispatches on), t entries after the round."""
+    hit = {}
+
+    def mark(what, name, cond):
+        if np.any(cond):
+            hit.setdefault(what, set()).add(name)
+
+    for name, c in cases.items():
+        if c.get("mode"):
+            continue
+        G, T = c["G"], c["T"]
+        rb = lanes(G)
+        for lo, hi in ((1, 4), (5, 8), (9, 16), (17, 32), (33, 64)):
+            mark(f"G in {lo}..{hi}", name, lo <= G <= hi)
+        mark("G == 32", name, G == 32)
+        mark("G == 33", name, G == 33)
+        rounds = sf.rounds_of(c)
+        restarts = []
+        for r, (seqs, seed, kw) in enumerate(rounds):
+            res = results[name][r]
+            if "gen" in c:
+                restarts.append(oracle.find_matches(seqs, seed, **kw)[2]["restarts"])
+            if r == 0:
+                continue
+            bucket, _, st = oracle.seed_probes(seqs, seed, table_size=T)
+            assert st["probes"] == res["probes"] == len(bucket)
+            nc = results[name][r - 1]["table_counts"].astype(np.int64)
+            K = np.bincount(bucket, minlength=T).astype(np.int64)
+            t = res["table_counts"].astype(np.int64)
+            v = nc + K
+            assert np.all(nc <= t) and np.all(t <= v)
+            mark("spill in mid-replay", name, (nc <= cap) & (cap < t))
+            mark("vector starts in global memory", name, nc > cap)
+            mark("v == kSmall", name, v == small)
+            mark("v == kSmall + 1", name, v == small + 1)
+            mark("long LDS-resident vector", name, (v > small) & (1000 <= nc) & (t - nc >= 1000) & (t <= cap))
+            mark(f"K > {rb}", name, K > rb)
+            mark("carried-only bucket", name, (K == 0) & (nc > 0))
+            mark("new-only bucket", name, (nc == 0) & (K > 0))
+            mark("one probe", name, res["probes"] == 1)
+            mark("no probe", name, res["probes"] == 0)
+        mark("restarts", name, len(restarts) > 0 and min(restarts) >= 1)
+    return hit
+
+
+def replay_constants():
+    """(kReplayLdsIds, kSmall of launch_replay_carried, lanes of the wide launch by G) read out of
+    the sources; replay_block is pinned by its text, a change of the lane counts fails here
+    instead of silently moving the edges the cases were chosen for."""
+    import os
+    import re
+    csrc = os.path.join(sf.ROOT, "libmems_amd", "csrc")
+    capi = open(os.path.join(csrc, "mums_capi.hip")).read()
+    replay = open(os.path.join(csrc, "replay.hip")).read()
+    cap = int(re.search(r"kReplayLdsIds\s*=\s*(\d+)", capi).group(1))
+    carried = replay[replay.index("hipError_t launch_replay_carried("):]
+    small = int(re.search(r"constexpr uint32_t kSmall\s*=\s*(\d+);", carried).group(1))
+    assert "constexpr int replay_block() { return MG <= 4 ? 1024 : (MG <= 8 ? 512 : 256); }" in replay
+    assert re.search(r"if \(G <= 4\) return find_replay<4>.*\n\s*if \(G <= 8\) return find_replay<8>.*\n"
+                     r"\s*if \(G <= 16\) return find_replay<16>.*\n\s*if \(G <= 32\) return find_replay<32>.*\n"
+                     r"\s*return find_replay<64>", capi)
+    return cap, small, lambda G: 1024 if G <= 4 else (512 if G <= 8 else 256)
+
+
+def test_cases_reach_the_carried_replays_paths(model, results):
+    """Every path replay_carried_kernel and launch_replay_carried choose among is reached by a
+    case, and by the case that exists for it (PATHS).  Conditions on the inputs, from the model
+    and the oracle's probes alone."""
+    cap, small, lanes = replay_constants()
+    assert (cap, small) == (8192, 64)
+    hit = carried_paths(results, sf.CASES, cap, small, lanes)
+    for what, names in PATHS.items():
+        for name in (names if isinstance(names, tuple) else (names,)):
+            assert name in hit.get(what, set()), f"{what}: not reached by {name} (reached by {sorted(hit.get(what, ()))})"
+    # round 1 of k12 makes one AddHashEntry call and it inserts
+    k12 = results["k12_one_probe"]
+    assert k12[1]["probes"] == 1 and len(k12[1]["log"][0]) == 1 and len(k12[1]["lengths"]) == len(k12[0]["lengths"]) + 1
+    # a round without probes (test_gpu_seed_family.py::test_round_without_probes_keeps_the_table)
+    seqs, seed, kw = sf.rounds_of(sf.FIRST)[0]
+    none = sf.run_model(model, [(seqs, seed, kw), ([b"A" * 60, b"C" * 60], seed, kw)])[1]
+    assert none["probes"] == 0 and len(none["lengths"]) == len(results[sf.FIRST][0]["lengths"]) > 0
+    # k1: the bucket is in LDS when round 1 starts and in global memory when round 2 starts
+    k1 = results["k1_spill_mid_replay"]
+    assert len(k1[0]["lengths"]) <= cap < len(k1[1]["lengths"])
+    assert "k1_spill_mid_replay" in hit["vector starts in global memory"]
