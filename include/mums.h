@@ -257,6 +257,46 @@ int  mums_eliminate_overlaps_v2(mums_ctx* ctx, const uint32_t* seq_ids, uint32_t
  * come from this context's FindMatches (Aligner.cpp:920 gap_list, :1580 mlist). */
 int  mums_load_matches(mums_ctx* ctx, uint32_t seq_count, uint64_t count, const uint64_t* lengths,
                        const int64_t* starts);
+/* B independent MemHash::FindMatches (MemHash.cpp:109-115), G sequences each, in one pass -- the
+ * gap searches of ProgressiveAligner::pairwiseAnchorSearch (ProgressiveAligner.cpp:589-678, called
+ * per pair of gap regions by recurseOnPairs, :681-) and of Aligner.cpp:784-, where the sequences
+ * are a few hundred to a few ten thousand bases and the fixed cost of mums_find is the whole cost.
+ * Sequence g of problem p = ascii[seq_off[p*G+g] .. seq_off[p*G+g+1]) (host memory, seq_off has
+ * B*G+1 non-decreasing entries).  Seed, table size, MaskedMemHash mask: the context's settings, the
+ * same for every problem; the seed must be set (pattern != 0, else MUMS_E_INVALID).
+ * Problem p's part of the result is bit for bit the MatchList FindMatches returns for p's sequences
+ * alone: starts 1-based in p's own sequences, GetMatchList (bucket-major) order, MER_REPEAT_LIMIT
+ * restarts included.
+ * The call starts as MemHash::Clear does (MemHash.cpp:76-93): sequences, results and a kept table
+ * go, the settings stay.  Afterwards the context holds one MatchList, the problems' lists in problem
+ * order (mums_result_count / mums_result_copy; seq_count = G), the offsets below, and in
+ * mums_get_stats the sums over the problems (seedmers, probes, mem_count, collision_count, restarts;
+ * ms_keys = upload + keys, ms_sort, ms_replay, ms_output, ms_total of the whole pass).
+ * On that list the calls that work on one problem's list or table return MUMS_E_UNSUPPORTED and
+ * leave it untouched: mums_multiplicity_filter, mums_length_filter, mums_eliminate_overlaps(_v2),
+ * mums_clear_sequences, mums_mem_table_count, mums_probe_copy, mums_copy_seed_keys(_range),
+ * mums_build_sml, mums_seed_occurrence, mums_write_sml (a problem's rows go through
+ * mums_load_matches on another context).  mums_clear, mums_find and mums_load_matches end that state.
+ * MemHash and MaskedMemHash (mums_set_mask) with repeat tolerance 0 and enumeration tolerance 1.
+ * MUMS_E_UNSUPPORTED with a message of its own, before any device work and with the context
+ * unchanged: other tolerances, PairwiseMatchFinder, the ParallelMemHash compat mode, start points,
+ * the match log, the progress log, sharded contexts.
+ * A sequence shorter than the seed, an empty one, a problem of empty sequences: no seed-mers from
+ * it, as in FindMatches (two sequences: no matches; match_off repeats).
+ * '-' in a sequence: MUMS_E_GAP, the message names the first such problem; the context is empty
+ * and usable.  B == 0: MUMS_OK, an empty list.  G < 2: MUMS_E_INVALID.  G up to 64.  The seed-mers
+ * of one batch must stay below 2^32 (else MUMS_E_UNSUPPORTED: split the batch).
+ * Inside the call some problems run through the single-problem pipeline and their rows are
+ * spliced in: a problem with more than 200000 seed-mers; one with a masked-key group above
+ * MER_REPEAT_LIMIT (a poly-A or N run of more than 1000 bases: SearchRange restarts,
+ * MatchFinder.cpp:253-277); and the largest problems of a batch where that is faster than
+ * holding the batched pass up for them.  The caller sees that only in restarts[]. */
+int  mums_find_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const char* ascii, const uint64_t* seq_off);
+/* After mums_find_batch: match_off[B+1] (problem p's matches are rows [match_off[p], match_off[p+1])
+ * of mums_result_copy); probes[B] = AddHashEntry calls (MemHash.cpp:209), collisions[B] =
+ * MemCollisionCount (MemHash.h:97), restarts[B] = MER_REPEAT_LIMIT restarts of problem p; any of
+ * the four may be NULL.  MUMS_E_INVALID when the context holds no batch result. */
+int  mums_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* probes, uint64_t* collisions, uint64_t* restarts);
 /* Test entry point: ids[0..n) = the permutation libstdc++ std::sort leaves on keys with
  * operator< (depth_override >= 0 forces the introsort depth limit; -1 = 2*lg(n)). */
 int  mums_debug_std_sort(mums_ctx* ctx, const uint64_t* keys, uint64_t n, int depth_override, uint32_t* ids);

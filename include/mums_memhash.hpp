@@ -272,6 +272,72 @@ public:
         write_progress();
         GetMatchList(ml);
     }
+    // Per-problem counters of the last FindMatchesBatch (mums_batch_info)
+    struct BatchCounters {
+        std::vector<uint64_t> probes, collisions, restarts;
+    };
+    // Many independent FindMatches in one device pass per seed pattern (mums_find_batch): the gap
+    // searches of one recurseOnPairs (ProgressiveAligner.cpp:681-).  problems[p] = the G sequences
+    // of problem p (the same G for all); out[p] = what FindMatches gives for them alone.  seeds
+    // empty: per problem getSeed(getDefaultSeedWeight(mean length), 0) as pairwiseAnchorSearch
+    // chooses it (:615-616, 625), a default weight of 0 gives an empty list and no search
+    // (:626-633); else one pattern per problem (0: no search).  Problems are grouped by pattern,
+    // one mums_find_batch per pattern.  Like Clear() + FindMatches the call drops the object's
+    // sequences and table, and it leaves the seed of the last group set.
+    virtual void FindMatchesBatch(const std::vector<std::vector<std::string>>& problems, std::vector<MatchList>& out,
+                                  const std::vector<uint64_t>& seeds = {}) {
+        const size_t B = problems.size();
+        if (!seeds.empty() && seeds.size() != B) throw InvalidData("FindMatchesBatch: one seed pattern per problem");
+        const size_t G = B ? problems[0].size() : 2;
+        out.assign(B, MatchList());
+        batch_ = BatchCounters();
+        batch_.probes.assign(B, 0);
+        batch_.collisions.assign(B, 0);
+        batch_.restarts.assign(B, 0);
+        std::vector<uint64_t> pats;      // distinct patterns in order of first appearance
+        std::vector<std::vector<size_t>> members;
+        for (size_t p = 0; p < B; ++p) {
+            if (problems[p].size() != G) throw InvalidData("FindMatchesBatch: every problem needs the same sequence count");
+            uint64_t pat = 0;
+            if (!seeds.empty()) {
+                pat = seeds[p];
+            } else {
+                uint64_t total = 0;
+                for (const std::string& s : problems[p]) total += s.size();
+                const uint32_t w = mums_default_seed_weight(G ? total / G : 0);
+                pat = w ? (uint64_t)mums_get_seed((int)w, 0) : 0;
+            }
+            if (pat == 0) continue;
+            size_t k = 0;
+            while (k < pats.size() && pats[k] != pat) ++k;
+            if (k == pats.size()) { pats.push_back(pat); members.emplace_back(); }
+            members[k].push_back(p);
+        }
+        if (pats.empty()) check(mums_clear(ctx_));
+        for (size_t k = 0; k < pats.size(); ++k) {
+            const std::vector<size_t>& idx = members[k];
+            std::string blob;
+            std::vector<uint64_t> off(1, 0);
+            for (size_t p : idx)
+                for (const std::string& s : problems[p]) {
+                    blob += s;
+                    off.push_back(blob.size());
+                }
+            check(mums_set_seed(ctx_, pats[k]));
+            check(mums_find_batch(ctx_, (uint32_t)idx.size(), (uint32_t)G, blob.data(), off.data()));
+            MatchList all;
+            GetMatchList(all);
+            std::vector<uint64_t> mo(idx.size() + 1), pr(idx.size()), co(idx.size()), rs(idx.size());
+            check(mums_batch_info(ctx_, mo.data(), pr.data(), co.data(), rs.data()));
+            for (size_t j = 0; j < idx.size(); ++j) {
+                out[idx[j]].assign(all.begin() + mo[j], all.begin() + mo[j + 1]);
+                batch_.probes[idx[j]] = pr[j];
+                batch_.collisions[idx[j]] = co[j];
+                batch_.restarts[idx[j]] = rs[j];
+            }
+        }
+    }
+    const BatchCounters& BatchInfo() const { return batch_; }
     // MemHash::CreateMatches (MemHash.cpp:104-107)
     virtual bool CreateMatches() {
         check(mums_find(ctx_));
@@ -459,6 +525,7 @@ protected:
     mums_ctx* ctx_ = nullptr;
     int device_ = 0;
     uint32_t repeat_tol_ = 0, enum_tol_ = 1, table_size_ = 40000;
+    BatchCounters batch_;
 };
 
 // MaskedMemHash (MaskedMemHash.h:25-40)

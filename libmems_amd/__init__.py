@@ -111,6 +111,7 @@ EXPORTED_SYMBOLS = [
     "mums_genome_device", "mums_shard_chain_label", "mums_shard_chain_export", "mums_shard_find_labelled",
     "mums_shard_chain_info", "mums_shard_chain_entries", "mums_shard_entry_thresholds", "mums_shard_kept_export",
     "mums_shard_find_kept", "mums_comm_exchange_info", "mums_eliminate_overlaps_v2", "mums_clear_sequences",
+    "mums_find_batch", "mums_batch_info",
 ]
 
 # mums_comm_ops (include/mums.h): the caller's transport as two host callbacks
@@ -235,6 +236,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mums_set_progress_log.argtypes = [vp, i32]
     lib.mums_progress_log_copy.argtypes = [vp, ctypes.c_char_p, u64, ctypes.POINTER(u64)]
     lib.mums_match_log_copy.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    lib.mums_find_batch.argtypes = [vp, u32, u32, vp, vp]
+    lib.mums_batch_info.argtypes = [vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -261,6 +264,32 @@ def getSeedWeight(seed: int) -> int:
 def getDefaultSeedWeight(avg_len: int) -> int:
     """SeedMasks.h:389-401."""
     return int(load_library().mums_default_seed_weight(avg_len))
+
+
+def batch_seed_groups(problems: Sequence[Sequence[bytes]], seeds: Optional[Sequence[int]] = None,
+                      default_weight=None, get_seed=None):
+    """The grouping of MemHash.FindMatchesBatch, host logic only: (patterns, groups).
+    patterns[p] = problem p's seed pattern: seeds[p], or with seeds=None
+    getSeed(getDefaultSeedWeight(mean length), 0) as pairwiseAnchorSearch chooses it
+    (ProgressiveAligner.cpp:615-616, 625); 0 when the default weight is 0 (below
+    MIN_DNA_SEED_WEIGHT: the early return at :626-633, no search).  groups = {pattern: [problem
+    indices in order]} for the patterns != 0, in order of first appearance."""
+    default_weight = default_weight or getDefaultSeedWeight
+    get_seed = get_seed or getSeed
+    if seeds is not None and len(seeds) != len(problems):
+        raise ValueError("FindMatchesBatch: one seed pattern per problem")
+    patterns: List[int] = []
+    groups: dict = {}
+    for p, prob in enumerate(problems):
+        if seeds is not None:
+            pat = int(seeds[p])
+        else:
+            w = default_weight(sum(len(s) for s in prob) // max(len(prob), 1))
+            pat = get_seed(w, 0) if w else 0
+        patterns.append(pat)
+        if pat:
+            groups.setdefault(pat, []).append(p)
+    return patterns, groups
 
 
 @dataclass
@@ -407,6 +436,56 @@ class MemHash:
             self._check(self._lib.mums_get_offset_log(self._ctx, out.ctypes.data, rows.value, ctypes.byref(rows),
                                                       ctypes.byref(g)))
         return out
+
+    def FindMatchesBatch(self, problems: Sequence[Sequence[bytes]], seeds: Optional[Sequence[int]] = None) -> List[MatchList]:
+        """Many independent FindMatches in one device pass per seed pattern (mums_find_batch): the
+        gap searches of one recurseOnPairs (ProgressiveAligner.cpp:681-).  problems: G-tuples of
+        bytes, the same G for all; returns one MatchList per problem, each what FindMatches gives
+        for that problem alone.  seeds=None: per problem getSeed(getDefaultSeedWeight(mean length),
+        0) (pairwiseAnchorSearch, :615-616, 625), a problem of default weight 0 gets an empty list
+        and no device work (:626-633); else one pattern per problem (0: empty list).  Problems
+        are grouped by pattern, one mums_find_batch per pattern.  Like Clear() + FindMatches, the
+        call drops the object's sequences and table; afterwards the object holds the last
+        group's list and seed pattern, and BatchInfo() every problem's counters."""
+        problems = [tuple(s.encode() if isinstance(s, str) else bytes(s) for s in prob) for prob in problems]
+        B = len(problems)
+        G = len(problems[0]) if B else 2
+        if any(len(prob) != G for prob in problems):
+            raise ValueError("FindMatchesBatch: every problem needs the same number of sequences")
+        patterns, groups = batch_seed_groups(problems, seeds)
+        out: List[Optional[MatchList]] = [None] * B
+        info = {k: np.zeros(B, dtype=np.uint64) for k in ("matches", "probes", "collisions", "restarts")}
+        self._keepalive.clear()
+        for p in range(B):
+            if patterns[p] == 0:
+                out[p] = MatchList(np.zeros(0, dtype=np.uint64), np.zeros((0, G), dtype=np.int64))
+        if not groups:
+            self._check(self._lib.mums_clear(self._ctx))
+        for pat, idx in groups.items():
+            blob = b"".join(s for p in idx for s in problems[p])
+            off = np.zeros(len(idx) * G + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(s) for p in idx for s in problems[p]], dtype=np.uint64)
+            self.SetSeed(pat)
+            self._check(self._lib.mums_find_batch(self._ctx, len(idx), G, blob, off.ctypes.data))
+            ml = self.GetMatchList()
+            mo = np.zeros(len(idx) + 1, dtype=np.uint64)
+            pr, co, rs = (np.zeros(len(idx), dtype=np.uint64) for _ in range(3))
+            self._check(self._lib.mums_batch_info(self._ctx, mo.ctypes.data, pr.ctypes.data, co.ctypes.data,
+                                                  rs.ctypes.data))
+            for k, p in enumerate(idx):
+                a, b = int(mo[k]), int(mo[k + 1])
+                out[p] = MatchList(ml.lengths[a:b].copy(), ml.starts[a:b].copy())
+                info["matches"][p] = b - a
+                info["probes"][p], info["collisions"][p], info["restarts"][p] = pr[k], co[k], rs[k]
+        self._batch_info = info
+        return out  # type: ignore[return-value]
+
+    def BatchInfo(self) -> dict:
+        """Per problem of the last FindMatchesBatch: matches, probes (AddHashEntry calls), collisions
+        (MemCollisionCount) and restarts (MER_REPEAT_LIMIT) as uint64 arrays."""
+        if getattr(self, "_batch_info", None) is None:
+            raise MumsError(MUMS_E_INVALID, "no FindMatchesBatch on this object")
+        return self._batch_info
 
     def CreateMatches(self) -> bool:
         """MemHash::CreateMatches (MemHash.cpp:104-107)."""
@@ -880,5 +959,5 @@ class PairwiseMatchFinder(MemHash):
 __all__ = [
     "MemHash", "MaskedMemHash", "ParallelMemHash", "PairwiseMatchFinder", "MatchList", "MumsError", "GapInSequence", "getSeed", "getSeedLength",
     "getSeedWeight", "getDefaultSeedWeight", "load_library", "EXPORTED_SYMBOLS", "STAGE_SEEDS", "STAGE_ALL", "ShardedMemHash",
-    "shard_key_ranges", "EliminateOverlaps", "EliminateOverlaps_v2",
+    "shard_key_ranges", "EliminateOverlaps", "EliminateOverlaps_v2", "batch_seed_groups",
 ]

@@ -160,6 +160,11 @@ struct mums_ctx {
     uint64_t fresh_coll = 0;
     bool list_edited = false;     // a filter / EliminateOverlaps / load_matches changed the list since
     EoWork eo;               // EliminateOverlaps work arrays (overlaps.hip)
+    // mums_find_batch (batch.hip): the context's list is the problems' lists in problem order
+    bool batch_result = false;
+    std::vector<uint64_t> batch_off, batch_probes, batch_coll, batch_restarts;   // B + 1 / B / B / B
+    mums_ctx* batch_sub = nullptr;   // problems the lanes leave out: the single-problem pipeline
+    DevBuf bt_ascii, bt_seg, bt_keys, bt_kA, bt_kB, bt_vA, bt_vB, bt_tmp, bt_ord, bt_pool, bt_per;
     bool match_log = false;  // MemHash::SetMatchLog: record the inserts (replay.hip)
     uint64_t log_n = 0;
     DevBuf logA, logB, logvA, logvB;
@@ -2135,6 +2140,13 @@ int check_ctx(mums_ctx* ctx) {
     return MUMS_OK;
 }
 
+// calls that work on one problem's list or table: refused while the context holds a batch's
+int batch_refused(mums_ctx* ctx, const char* what) {
+    if (!ctx->batch_result) return MUMS_OK;
+    return fail(ctx, MUMS_E_UNSUPPORTED, std::string(what) + " on the result of mums_find_batch (copy the problem's "
+                                                             "rows and use mums_load_matches)");
+}
+
 // MSD bits of the sharded key exchange: at least the packed-record split (2w+1-32),
 // else 8 (256 key ranges to balance over the ranks), never the parity bit.
 int shard_msd_bits(int w) {
@@ -2249,7 +2261,9 @@ int mums_ctx_destroy(mums_ctx* ctx) {
                       &ctx->logA, &ctx->logB, &ctx->logvA, &ctx->logvB, &ctx->tiebuf, &ctx->fk, &ctx->fkloc,
                       &ctx->crbuf, &ctx->crcnt, &ctx->crlive, &ctx->crruns, &ctx->crall, &ctx->fsk, &ctx->bst2,
                       &ctx->side, &ctx->bst8, &ctx->cbst, &ctx->dsarr, &ctx->labx, &ctx->rkpool0, &ctx->rkpool1,
-                      &ctx->rku32, &ctx->ascii_all, &ctx->keep_pool, &ctx->keep_cnt};
+                      &ctx->rku32, &ctx->ascii_all, &ctx->keep_pool, &ctx->keep_cnt, &ctx->bt_ascii, &ctx->bt_seg,
+                      &ctx->bt_keys, &ctx->bt_kA, &ctx->bt_kB, &ctx->bt_vA, &ctx->bt_vB, &ctx->bt_tmp, &ctx->bt_ord,
+                      &ctx->bt_pool, &ctx->bt_per};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i < EV_COUNT; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
@@ -2258,6 +2272,7 @@ int mums_ctx_destroy(mums_ctx* ctx) {
     for (int i = 0; i < 6; ++i)
         if (ctx->ev_walk[i]) (void)hipEventDestroy(ctx->ev_walk[i]);
     if (ctx->compat_sub) (void)mums_ctx_destroy(ctx->compat_sub);
+    if (ctx->batch_sub) (void)mums_ctx_destroy(ctx->batch_sub);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return MUMS_OK;
@@ -2345,6 +2360,11 @@ int mums_clear(mums_ctx* ctx) {
     ctx->keep_on = ctx->table_fresh = ctx->list_edited = false;
     ctx->keep_n = ctx->keep_coll = ctx->carry_coll = 0;
     ctx->pool_c = 0;
+    ctx->batch_result = false;
+    ctx->batch_off.clear();
+    ctx->batch_probes.clear();
+    ctx->batch_coll.clear();
+    ctx->batch_restarts.clear();
     return MUMS_OK;
 }
 
@@ -2352,6 +2372,7 @@ int mums_clear(mums_ctx* ctx) {
 // hash table (mem_table, mem_table_count, m_mem_count, m_collision_count) stays for the next find
 int mums_clear_sequences(mums_ctx* ctx) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (batch_refused(ctx, "ClearSequences")) return MUMS_E_UNSUPPORTED;
     if (ctx->shard) return fail(ctx, MUMS_E_UNSUPPORTED, "ClearSequences on a sharded context");
     HIPCHK(hipSetDevice(ctx->device));
     if (ctx->table_fresh) {   // a completed find since the last Clear / ClearSequences: its table is kept
@@ -2396,6 +2417,7 @@ int mums_find_stage(mums_ctx* ctx, int stage) {
     if (!have_device()) return fail(ctx, MUMS_E_NODEVICE, "no HIP device");
     if (ctx->shard) return fail(ctx, MUMS_E_INVALID, "context is in sharded mode: use mums_shard_keys/merge");
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->batch_result = false;   // the context's list becomes this find's
     std::vector<uint64_t> lens;
     for (auto& g : ctx->genomes) lens.push_back(g.n);
     int rc = prepare_run(ctx, lens);
@@ -2490,6 +2512,7 @@ int mums_result_copy(mums_ctx* ctx, uint64_t* lengths, int64_t* starts) {
 
 int mums_mem_table_count(mums_ctx* ctx, uint32_t* counts, uint32_t table_size) {
     if (check_ctx(ctx) || !counts) return MUMS_E_INVALID;
+    if (batch_refused(ctx, "MemTableCount")) return MUMS_E_UNSUPPORTED;
     if (ctx->stage_done < MUMS_STAGE_ALL && ctx->keep_on) {   // after ClearSequences: the kept table's counts
         if (ctx->keep_n == 0) {
             std::fill(counts, counts + table_size, 0u);
@@ -2527,6 +2550,7 @@ int mums_set_profiling(mums_ctx* ctx, int enable) {
 
 int mums_copy_seed_keys(mums_ctx* ctx, uint32_t genome, uint64_t* out, uint64_t cap) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (batch_refused(ctx, "seed key export")) return MUMS_E_UNSUPPORTED;
     if (ctx->stage_done < MUMS_STAGE_SEEDS) return fail(ctx, MUMS_E_INVALID, "keys not computed yet");
     if (genome >= ctx->genomes.size()) return fail(ctx, MUMS_E_INVALID, "genome index out of range");
     const uint64_t m = ctx->gt.m[genome];
@@ -2543,6 +2567,7 @@ int mums_copy_seed_keys(mums_ctx* ctx, uint32_t genome, uint64_t* out, uint64_t 
 
 int mums_copy_seed_keys_range(mums_ctx* ctx, uint32_t genome, uint64_t first, uint64_t count, uint64_t* out) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (batch_refused(ctx, "seed key export")) return MUMS_E_UNSUPPORTED;
     if (ctx->stage_done < MUMS_STAGE_SEEDS) return fail(ctx, MUMS_E_INVALID, "keys not computed yet");
     if (genome >= ctx->genomes.size()) return fail(ctx, MUMS_E_INVALID, "genome index out of range");
     const uint64_t m = ctx->gt.m[genome];
@@ -2601,6 +2626,7 @@ int genome_sml(mums_ctx* ctx, uint32_t genome, const uint64_t** sk, const uint32
 
 int mums_build_sml(mums_ctx* ctx, uint32_t genome, uint32_t* positions, uint64_t cap) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (batch_refused(ctx, "SortedMerList export")) return MUMS_E_UNSUPPORTED;
     if (ctx->stage_done < MUMS_STAGE_SEEDS) return fail(ctx, MUMS_E_INVALID, "keys not sorted yet");
     if (genome >= ctx->genomes.size()) return fail(ctx, MUMS_E_INVALID, "genome index out of range");
     const uint64_t m = ctx->gt.m[genome];
@@ -2617,6 +2643,7 @@ int mums_build_sml(mums_ctx* ctx, uint32_t genome, uint32_t* positions, uint64_t
 
 int mums_seed_occurrence(mums_ctx* ctx, uint32_t genome, float* freq, uint64_t cap) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (batch_refused(ctx, "SeedOccurrenceList")) return MUMS_E_UNSUPPORTED;
     if (ctx->stage_done < MUMS_STAGE_SEEDS) return fail(ctx, MUMS_E_INVALID, "keys not computed yet");
     if (genome >= ctx->genomes.size()) return fail(ctx, MUMS_E_INVALID, "genome index out of range");
     const uint64_t m = ctx->gt.m[genome], n = ctx->gt.n[genome];
@@ -2672,6 +2699,7 @@ void basic_dna_table(uint8_t* t) {   // SortedMerList::CreateBasicDNATable (Sort
 
 int mums_write_sml(mums_ctx* ctx, uint32_t genome, const char* path, const char* description) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (batch_refused(ctx, "SortedMerList file")) return MUMS_E_UNSUPPORTED;
     if (ctx->stage_done < MUMS_STAGE_SEEDS) return fail(ctx, MUMS_E_INVALID, "keys not computed yet");
     if (genome >= ctx->genomes.size()) return fail(ctx, MUMS_E_INVALID, "genome index out of range");
     if (!path) return fail(ctx, MUMS_E_INVALID, "null path");
@@ -2749,6 +2777,7 @@ int mums_add_genome_sml(mums_ctx* ctx, const char* path, uint64_t* seed_out) {
 // MultiplicityFilter / LengthFilter (MatchList.h:636-664) on the context's MatchList
 int match_filter(mums_ctx* ctx, uint32_t mult, uint64_t min_len) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (batch_refused(ctx, "MatchList filter")) return MUMS_E_UNSUPPORTED;
     if (ctx->stage_done < MUMS_STAGE_ALL) return fail(ctx, MUMS_E_INVALID, "no completed FindMatches on this context");
     HIPCHK(hipSetDevice(ctx->device));
     const int G = ctx->gt.G;
@@ -3071,6 +3100,7 @@ int mums_match_log_copy(mums_ctx* ctx, uint64_t* lengths, int64_t* starts, uint6
 // EliminateOverlaps (Aligner.cpp:62-176) on the context's MatchList, in place
 int mums_eliminate_overlaps(mums_ctx* ctx) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (batch_refused(ctx, "EliminateOverlaps")) return MUMS_E_UNSUPPORTED;
     if (ctx->stage_done < MUMS_STAGE_ALL) return fail(ctx, MUMS_E_INVALID, "no completed FindMatches on this context");
     if (ctx->M >= 0xFFFFFFF0ull) return fail(ctx, MUMS_E_UNSUPPORTED, "EliminateOverlaps of more than 2^32 matches");
     HIPCHK(hipSetDevice(ctx->device));
@@ -3091,6 +3121,7 @@ int mums_eliminate_overlaps(mums_ctx* ctx) {
 // EliminateOverlaps_v2 (ProgressiveAligner.h:300-406) on the context's MatchList, in place
 int mums_eliminate_overlaps_v2(mums_ctx* ctx, const uint32_t* seq_ids, uint32_t count, int eliminate_both) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (batch_refused(ctx, "EliminateOverlaps_v2")) return MUMS_E_UNSUPPORTED;
     if (ctx->stage_done < MUMS_STAGE_ALL) return fail(ctx, MUMS_E_INVALID, "no completed FindMatches on this context");
     if (ctx->M >= 0xFFFFFFF0ull) return fail(ctx, MUMS_E_UNSUPPORTED, "EliminateOverlaps_v2 of more than 2^32 matches");
     const int G = ctx->gt.G;
@@ -3136,7 +3167,322 @@ int mums_load_matches(mums_ctx* ctx, uint32_t seq_count, uint64_t count, const u
     ctx->M = count;
     ctx->P = 0;
     ctx->list_edited = true;
+    ctx->batch_result = false;
     ctx->stage_done = MUMS_STAGE_ALL;
+    return MUMS_OK;
+}
+
+// ---- mums_find_batch: B independent FindMatches in one pass (batch.hip) ----
+// seed-mers of one problem the lanes take; a larger problem runs through the single-problem
+// pipeline, whose tiles it fills (MUMS_DEV_BATCH_CAP: development A/B)
+static uint64_t batch_problem_cap() {
+    const char* e = getenv("MUMS_DEV_BATCH_CAP");
+    return e ? strtoull(e, nullptr, 10) : 200000ull;
+}
+
+// problem p alone on the sub-context: its list appended to len / s, its counters
+static int batch_single(mums_ctx* ctx, uint32_t G, const char* ascii, const uint64_t* so, std::vector<uint64_t>& len,
+                        std::vector<int64_t>& s, uint64_t* count, uint64_t* probes, uint64_t* coll, uint64_t* restarts) {
+    if (!ctx->batch_sub) {
+        const int rc = mums_ctx_create(ctx->device, &ctx->batch_sub);
+        if (rc != MUMS_OK) return fail(ctx, rc, "mums_find_batch: no context for the single-problem pipeline");
+    }
+    mums_ctx* sub = ctx->batch_sub;
+    int rc = mums_clear(sub);
+    if (!rc) rc = mums_set_seed(sub, ctx->seed);
+    if (!rc) rc = mums_set_params(sub, 0, 1, ctx->table_size);
+    if (!rc) rc = mums_set_mask(sub, ctx->masked, ctx->seq_mask);
+    for (uint32_t g = 0; g < G && !rc; ++g) rc = mums_add_genome(sub, ascii + so[g], so[g + 1] - so[g]);
+    if (!rc) rc = mums_find(sub);
+    uint64_t M = 0;
+    if (!rc) rc = mums_result_count(sub, &M, nullptr);
+    if (!rc && M) {
+        const size_t l0 = len.size(), s0 = s.size();
+        len.resize(l0 + M);
+        s.resize(s0 + M * (size_t)G);
+        rc = mums_result_copy(sub, len.data() + l0, s.data() + s0);
+    }
+    if (rc) return fail(ctx, rc, std::string("mums_find_batch, single-problem pipeline: ") + sub->err);
+    *count = M;
+    *probes = sub->st.probes;
+    *coll = sub->st.collision_count;
+    *restarts = sub->st.restarts;
+    (void)mums_clear(sub);
+    return MUMS_OK;
+}
+
+int mums_find_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const char* ascii, const uint64_t* seq_off) {
+    if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (!have_device()) return fail(ctx, MUMS_E_NODEVICE, "no HIP device");
+    // modes outside the batched scope, before anything changes
+    if (ctx->shard || ctx->slice) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch on a sharded context");
+    if (ctx->pairwise) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: PairwiseMatchFinder is not batched");
+    if (ctx->pcompat) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: the ParallelMemHash compat mode is not batched");
+    if (ctx->repeat_tol != 0 || ctx->enum_tol != 1)
+        return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: repeat tolerance 0 and enumeration tolerance 1 only");
+    if (have_start_points(ctx)) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: start points are not batched");
+    if (ctx->match_log) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: the match log (SetMatchLog) is not batched");
+    if (ctx->progress_on) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: the progress log (LogProgress) is not batched");
+    if (G < 2) return fail(ctx, MUMS_E_INVALID, "mums_find_batch: at least two sequences per problem");
+    if (G > (uint32_t)kMaxG) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: more than 64 sequences per problem");
+    if (ctx->seed == 0) return fail(ctx, MUMS_E_INVALID, "mums_find_batch: the seed pattern must be set (mums_set_seed)");
+    const uint64_t nseg = (uint64_t)B * G;
+    if (nseg + 1 >= (1ull << 32)) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: more than 2^32 sequences");
+    if (B && !seq_off) return fail(ctx, MUMS_E_INVALID, "mums_find_batch: null sequence offsets");
+    for (uint64_t s = 0; s < nseg; ++s)
+        if (seq_off[s + 1] < seq_off[s]) return fail(ctx, MUMS_E_INVALID, "mums_find_batch: sequence offsets decrease");
+    const uint64_t a0 = B ? seq_off[0] : 0, A = B ? seq_off[nseg] - a0 : 0;
+    if (A && !ascii) return fail(ctx, MUMS_E_INVALID, "Null gnSequence pointer");
+    const uint64_t pat = ctx->seed;
+    const int L = seed_len(pat), w = __builtin_popcountll(pat);
+    if (L > 32) return fail(ctx, MUMS_E_INVALID, "Mer size is too large");
+    if (w > 31) return fail(ctx, MUMS_E_UNSUPPORTED, "seed weight 32 not supported");
+    // the sequences' seed-mers; the lanes' pass takes every problem up to the cap
+    const int kbits = 2 * w + 1, pbits = ceil_log2(B ? B : 1);
+    const bool lanes = kbits + pbits <= 64;
+    const uint64_t cap = batch_problem_cap();
+    std::vector<uint32_t> mbase(nseg + 1, 0);
+    std::vector<uint64_t> aoff(nseg + 1, 0), nlen(nseg + 1, 0);
+    std::vector<uint8_t> routed(B, 0);
+    std::vector<uint64_t> recs(B, 0);
+    uint64_t Nall = 0, N = 0;
+    for (uint32_t p = 0; p < B; ++p) {
+        uint64_t r = 0;
+        for (uint32_t g = 0; g < G; ++g) {
+            const uint64_t n = seq_off[(uint64_t)p * G + g + 1] - seq_off[(uint64_t)p * G + g];
+            r += n < (uint64_t)L ? 0 : n - L + 1;
+        }
+        recs[p] = r;
+        Nall += r;
+        routed[p] = (!lanes || r > cap) ? 1 : 0;
+        if (Nall >= 0xFFFFFFF0ull)
+            return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: 2^32 seed-mers or more in one batch (split it)");
+    }
+    // The lanes run side by side, so their pass lasts as long as its largest problem (about
+    // kLaneUs per seed-mer), while a problem run alone costs about kSingleUs whatever its size:
+    // the k largest problems run alone, k minimising the sum of the two
+    std::vector<uint32_t> order(B);
+    for (uint32_t p = 0; p < B; ++p) order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        return (routed[x] ? ~0ull : recs[x]) > (routed[y] ? ~0ull : recs[y]);
+    });
+    if (lanes && !getenv("MUMS_DEV_BATCH_NO_SPLIT")) {
+        constexpr double kLaneUs = 10.0, kSingleUs = 1000.0;
+        uint32_t k0 = 0, best = 0;
+        while (k0 < B && routed[order[k0]]) ++k0;
+        double best_cost = -1;
+        for (uint32_t k = k0; k <= B; ++k) {
+            const double cost = kLaneUs * (double)(k < B ? recs[order[k]] : 0) + kSingleUs * (double)(k - k0);
+            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = k; }
+        }
+        for (uint32_t k = k0; k < best; ++k) routed[order[k]] = 1;
+    }
+    for (uint64_t s = 0; s < nseg; ++s) {
+        const uint64_t n = seq_off[s + 1] - seq_off[s];
+        aoff[s] = seq_off[s] - a0;
+        nlen[s] = n;
+        mbase[s] = (uint32_t)N;
+        if (!routed[s / G]) N += n < (uint64_t)L ? 0 : n - L + 1;
+    }
+    mbase[nseg] = (uint32_t)N;
+
+    // starts as MemHash::Clear does
+    int rc = mums_clear(ctx);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->pattern = pat;
+    ctx->L = L;
+    ctx->w = w;
+    ctx->ss = make_seed_spec(pat, L, w);
+    ctx->gt = GenomeTable{};
+    ctx->gt.G = (int)G;
+    ctx->batch_off.assign((size_t)B + 1, 0);
+    ctx->batch_probes.assign(B, 0);
+    ctx->batch_coll.assign(B, 0);
+    ctx->batch_restarts.assign(B, 0);
+    auto done = [&](uint64_t M, uint64_t P) {
+        ctx->M = M;
+        ctx->P = P;
+        ctx->N = Nall;
+        ctx->batch_result = true;
+        ctx->list_edited = true;
+        ctx->stage_done = MUMS_STAGE_ALL;
+        return MUMS_OK;
+    };
+    if (B == 0) return done(0, 0);
+
+    hipStream_t st = ctx->stream;
+    (void)hipEventRecord(ctx->ev[EV_START], st);
+    // per-problem device words: cnt, probes, coll, flag (B each), pool cursor, first '-' offset
+    const size_t per_words = (size_t)4 * B + 4;
+    HIPCHK(ctx->bt_per.ensure(per_words * 4 + 64));
+    uint32_t* d_cnt = ctx->bt_per.as<uint32_t>();
+    uint32_t *d_probes = d_cnt + B, *d_coll = d_cnt + 2 * (size_t)B, *d_flag = d_cnt + 3 * (size_t)B;
+    uint32_t* d_pool_n = d_cnt + 4 * (size_t)B;
+    unsigned long long* d_first = (unsigned long long*)(d_pool_n + 2);
+    HIPCHK(hipMemsetAsync(ctx->bt_per.p, 0, ((size_t)4 * B + 2) * 4, st));
+    HIPCHK(hipMemsetAsync(d_first, 0xFF, 8, st));
+    HIPCHK(ctx->bt_ascii.ensure(A + 64));
+    if (A) HIPCHK(hipMemcpyAsync(ctx->bt_ascii.p, ascii + a0, A, hipMemcpyHostToDevice, st));
+    // segment tables: aoff (nseg + 1 u64), nlen (nseg + 1 u64), doff (B u64), mbase (nseg + 1 u32), order (B u32)
+    const size_t seg_bytes = (2 * (nseg + 1) + B) * 8 + (nseg + 1 + B) * 4;
+    HIPCHK(ctx->bt_seg.ensure(seg_bytes + 64));
+    uint64_t* d_aoff = ctx->bt_seg.as<uint64_t>();
+    uint64_t *d_nlen = d_aoff + nseg + 1, *d_doff = d_nlen + nseg + 1;
+    uint32_t* d_mbase = (uint32_t*)(d_doff + B);
+    uint32_t* d_order = d_mbase + nseg + 1;
+    // (order: problems of similar size share a wave; the ones run alone come first and have no seed-mers here)
+    HIPCHK(hipMemcpyAsync(d_aoff, aoff.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_nlen, nlen.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_mbase, mbase.data(), (nseg + 1) * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(launch_batch_gap(ctx->bt_ascii.as<char>(), 0, A, d_first, st));
+    unsigned long long first_gap = ~0ull;
+    HIPCHK(hipMemcpyAsync(&first_gap, d_first, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (first_gap != ~0ull) {   // SortedMerList.cpp:433-437 throws for the sequence holding it
+        const uint64_t at = a0 + first_gap;
+        const uint64_t s = (uint64_t)(std::upper_bound(seq_off, seq_off + nseg + 1, at) - seq_off) - 1;
+        ctx->batch_off.clear();
+        ctx->batch_probes.clear();
+        ctx->batch_coll.clear();
+        ctx->batch_restarts.clear();
+        return fail(ctx, MUMS_E_GAP, "Gap in genome sequence: problem " + std::to_string(s / G) + " of the batch");
+    }
+
+    std::vector<uint32_t> per((size_t)4 * B, 0);
+    if (N > 0) {
+        const uint64_t pool_cap64 = std::min<uint64_t>(N / 2 + 1, std::max<uint64_t>(N / 8, 1ull << 16));
+        HIPCHK(ctx->bt_keys.ensure(N * 8 + 64));
+        HIPCHK(ctx->bt_kA.ensure(N * 8 + 64));
+        HIPCHK(ctx->bt_kB.ensure(N * 8 + 64));
+        HIPCHK(ctx->bt_vA.ensure(N * 4 + 64));
+        HIPCHK(ctx->bt_vB.ensure(N * 4 + 64));
+        HIPCHK(ctx->bt_tmp.ensure(radix_tmp_bytes(N) + 256));
+        HIPCHK(ctx->bt_ord.ensure((N / 2 + 2) * 8));
+        HIPCHK(ctx->bt_pool.ensure(pool_cap64 * (size_t)(G + 2) * 8 + 64));
+        HIPCHK(launch_batch_keys(ctx->bt_ascii.as<char>(), d_aoff, d_mbase, (uint32_t)nseg, G, (uint32_t)N, ctx->ss, kbits,
+                                 ctx->bt_keys.as<uint64_t>(), st));
+        (void)hipEventRecord(ctx->ev[EV_KEYS], st);
+        int ob = 0;
+        HIPCHK(radix_sort<uint64_t>(ctx->bt_keys.as<uint64_t>(), nullptr, N, kbits + pbits, ctx->bt_kA.as<uint64_t>(),
+                                    ctx->bt_vA.as<uint32_t>(), ctx->bt_kB.as<uint64_t>(), ctx->bt_vB.as<uint32_t>(),
+                                    ctx->bt_tmp.p, &ob, st));
+        (void)hipEventRecord(ctx->ev[EV_SORT], st);
+        BatchReplay br{};
+        br.sk = ob == 0 ? ctx->bt_kA.as<uint64_t>() : ctx->bt_kB.as<uint64_t>();
+        br.sv = ob == 0 ? ctx->bt_vA.as<uint32_t>() : ctx->bt_vB.as<uint32_t>();
+        br.keys = ctx->bt_keys.as<uint64_t>();
+        br.mbase = d_mbase;
+        br.nlen = d_nlen;
+        br.order = d_order;
+        br.ord = ctx->bt_ord.as<uint64_t>();
+        br.pool = ctx->bt_pool.as<int64_t>();
+        br.pool_cap = (uint32_t)pool_cap64;
+        br.pool_n = d_pool_n;
+        br.cnt = d_cnt;
+        br.probes = d_probes;
+        br.coll = d_coll;
+        br.flag = d_flag;
+        br.B = B;
+        br.G = G;
+        br.L = L;
+        br.kbits = kbits;
+        br.table_size = ctx->table_size;
+        br.masked = ctx->masked;
+        br.seq_mask = ctx->seq_mask;
+        HIPCHK(launch_batch_replay(br, st));
+        (void)hipEventRecord(ctx->ev[EV_REPLAY], st);
+        HIPCHK(hipMemcpyAsync(per.data(), d_cnt, (size_t)4 * B * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    } else {
+        (void)hipEventRecord(ctx->ev[EV_KEYS], st);
+        (void)hipEventRecord(ctx->ev[EV_SORT], st);
+        (void)hipEventRecord(ctx->ev[EV_REPLAY], st);
+    }
+    const uint32_t *h_cnt = per.data(), *h_probes = h_cnt + B, *h_coll = h_cnt + 2 * (size_t)B, *h_flag = h_cnt + 3 * (size_t)B;
+
+    // the problems left out (above the cap) or not finished (MER_REPEAT_LIMIT, pool) run alone
+    std::vector<uint64_t> rlen;
+    std::vector<int64_t> rs;
+    std::vector<uint64_t> rcount(B, 0), rfirst(B, 0);
+    uint64_t nrouted = 0;
+    for (uint32_t p = 0; p < B; ++p) {
+        if (!routed[p] && !h_flag[p]) {
+            ctx->batch_probes[p] = h_probes[p];
+            ctx->batch_coll[p] = h_coll[p];
+            continue;
+        }
+        routed[p] = 1;
+        ++nrouted;
+        rfirst[p] = rlen.size();
+        rc = batch_single(ctx, G, ascii, seq_off + (uint64_t)p * G, rlen, rs, &rcount[p], &ctx->batch_probes[p],
+                          &ctx->batch_coll[p], &ctx->batch_restarts[p]);
+        if (rc) {
+            const std::string msg = ctx->err;
+            (void)mums_clear(ctx);
+            return fail(ctx, rc, msg);
+        }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    uint64_t M = 0, P = 0, C = 0, R = 0;
+    std::vector<uint64_t> doff(B);
+    for (uint32_t p = 0; p < B; ++p) {
+        ctx->batch_off[p] = M;
+        doff[p] = M;
+        M += routed[p] ? rcount[p] : h_cnt[p];
+        P += ctx->batch_probes[p];
+        C += ctx->batch_coll[p];
+        R += ctx->batch_restarts[p];
+    }
+    ctx->batch_off[B] = M;
+    HIPCHK(ctx->out_len.ensure((M + 1) * 8));
+    HIPCHK(ctx->out_s.ensure((M + 1) * (size_t)G * 8 + 8));
+    if (M > 0) {
+        if (N > 0) {
+            HIPCHK(hipMemcpyAsync(d_doff, doff.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(launch_batch_emit(ctx->bt_ord.as<uint64_t>(), ctx->bt_pool.as<int64_t>(), d_mbase, d_cnt, d_doff, B, G,
+                                     ctx->out_len.as<uint64_t>(), ctx->out_s.as<int64_t>(), st));
+        }
+        for (uint32_t p = 0; p < B && nrouted; ++p) {
+            if (!routed[p] || rcount[p] == 0) continue;
+            HIPCHK(hipMemcpyAsync(ctx->out_len.as<uint64_t>() + doff[p], rlen.data() + rfirst[p], rcount[p] * 8,
+                                  hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ctx->out_s.as<int64_t>() + doff[p] * G, rs.data() + rfirst[p] * G,
+                                  rcount[p] * (size_t)G * 8, hipMemcpyHostToDevice, st));
+        }
+    }
+    (void)hipEventRecord(ctx->ev[EV_OUTPUT], st);
+    HIPCHK(hipStreamSynchronize(st));
+    mums_stats& s = ctx->st;
+    s = mums_stats{};
+    s.seedmers = Nall;
+    s.probes = P;
+    s.mem_count = M;
+    s.collision_count = C;
+    s.restarts = R;
+    s.repeat_limit_groups = R;
+    s.key_bytes = 8;
+    s.sort_passes = (uint64_t)((kbits + pbits + 7) / 8);
+    auto ms = [&](int a, int b) {
+        float f = 0;
+        return hipEventElapsedTime(&f, ctx->ev[a], ctx->ev[b]) == hipSuccess ? (double)f : 0.0;
+    };
+    s.ms_keys = ms(EV_START, EV_KEYS);
+    s.ms_sort = ms(EV_KEYS, EV_SORT);
+    s.ms_replay = ms(EV_SORT, EV_REPLAY);
+    s.ms_output = ms(EV_REPLAY, EV_OUTPUT);
+    s.ms_total = ms(EV_START, EV_OUTPUT);
+    return done(M, P);
+}
+
+int mums_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* probes, uint64_t* collisions, uint64_t* restarts) {
+    if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (!ctx->batch_result) return fail(ctx, MUMS_E_INVALID, "no completed mums_find_batch on this context");
+    if (match_off) std::copy(ctx->batch_off.begin(), ctx->batch_off.end(), match_off);
+    if (probes) std::copy(ctx->batch_probes.begin(), ctx->batch_probes.end(), probes);
+    if (collisions) std::copy(ctx->batch_coll.begin(), ctx->batch_coll.end(), collisions);
+    if (restarts) std::copy(ctx->batch_restarts.begin(), ctx->batch_restarts.end(), restarts);
     return MUMS_OK;
 }
 
@@ -4286,6 +4632,7 @@ int mums_probe_count(mums_ctx* ctx, uint64_t* count) {
 
 int mums_probe_copy(mums_ctx* ctx, uint32_t* buckets, uint64_t* ref_index, uint64_t capacity) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (batch_refused(ctx, "probe export")) return MUMS_E_UNSUPPORTED;
     if (ctx->stage_done < MUMS_STAGE_SEEDS) return fail(ctx, MUMS_E_INVALID, "no seed stage run");
     if (ctx->shard && ctx->merge_chunked)
         return fail(ctx, MUMS_E_UNSUPPORTED, "probe export after a chunked shard merge");

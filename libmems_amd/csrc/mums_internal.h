@@ -706,6 +706,39 @@ hipError_t launch_cr_live_compact(const CrStream& s, const GenomeTable& gt, cons
                                   const uint32_t* bstart, uint32_t nb, uint32_t* dst_bstart, uint32_t* d_total,
                                   hipStream_t st, const uint64_t* goff = nullptr);
 
+// batch.hip: B independent FindMatches of G sequences each in one pass (mums_find_batch).
+// Sequence s = p * G + g: ASCII at ascii + aoff[s], its seed-mers at compact indices
+// [mbase[s], mbase[s + 1]) (mbase[B * G] = N < 2^32; a sequence left out of the pass has none).
+hipError_t launch_batch_gap(const char* ascii, uint64_t lo, uint64_t hi, unsigned long long* d_first, hipStream_t st);
+// keys[i] = p << kbits | ckey of compact index i (kbits = 2w+1)
+hipError_t launch_batch_keys(const char* ascii, const uint64_t* aoff, const uint32_t* mbase, uint32_t nseg, uint32_t G,
+                             uint32_t N, const SeedSpec& ss, int kbits, uint64_t* keys, hipStream_t st);
+struct BatchReplay {
+    const uint64_t* sk;       // keys sorted (stable), sv = their compact indices
+    const uint32_t* sv;
+    const uint64_t* keys;     // keys by compact index
+    const uint32_t* mbase;
+    const uint64_t* nlen;     // B * G sequence lengths
+    const uint32_t* order;    // lane -> problem
+    uint64_t* ord;            // N / 2 + 1 words: every problem's table as (bucket << 32 | entry), bucket-major
+    int64_t* pool;            // pool_cap entries {length, offset, starts}
+    uint32_t pool_cap;
+    uint32_t* pool_n;         // entries taken (zeroed by the caller)
+    uint32_t *cnt, *probes, *coll, *flag;   // per problem: entries, AddHashEntry calls, collisions, 0 = done
+    uint32_t B, G;
+    int L, kbits;
+    uint32_t table_size;
+    int masked;
+    uint64_t seq_mask;
+};
+// flag[p] != 0: the problem was not finished (1: a masked-key group above MER_REPEAT_LIMIT, 2: the
+// entry pool is full, 4: internal) and has no entries; the caller runs it alone
+hipError_t launch_batch_replay(const BatchReplay& b, hipStream_t st);
+// problem p's entries -> rows [doff[p], doff[p] + cnt[p]) of the MatchList
+hipError_t launch_batch_emit(const uint64_t* ord, const int64_t* pool, const uint32_t* mbase, const uint32_t* cnt,
+                             const uint64_t* doff, uint32_t B, uint32_t G, uint64_t* out_len, int64_t* out_s,
+                             hipStream_t st);
+
 // smlsort.hip: the std::sort order of equal seed mers in every SortedMerList
 // (MemorySML.cpp:54) for flagged runs.  Slot space = genome-major SML slots (= global
 // seed-mer indices); flags: pf[t] = 1 when sorted slots t, t + 1 form a pair of a run that

@@ -9,6 +9,10 @@
 //       MemHash::FindMatches from ml.sml_table; stderr reports the SMLs materialised (0)
 //   mums_find family G n weight p            progressiveMauve's seed family: Clear, then seed ranks
 //       0-2 each ClearSequences + FindMatches on one MemHash (ProgressiveAligner.cpp:619-653)
+//   mums_find batch B n p [mask]             B problems of two sequences (lengths n / (k + 1), the
+//       Appendix-C generator seeded per problem): "# problem k" + its MatchList text, first from
+//       MemHash::FindMatchesBatch (default seeds), then after "== loop" from a loop of
+//       Clear + FindMatches with the same seeds on the same object
 //   mums_find smldump G n weight p g stride  genome g's deferred SML read back: every entry
 //       (position, mer) through operator[], then FindMer of every stride-th entry's mer
 #include <unistd.h>
@@ -126,6 +130,51 @@ int main(int argc, char** argv) {
                       << std::chrono::duration<double, std::milli>(t1 - t0).count() << " find ms "
                       << std::chrono::duration<double, std::milli>(t2 - t1).count() << " materialized "
                       << mums::HipSML::Materializations() << "\n";
+        } catch (const std::exception& e) {
+            std::cerr << "error: " << e.what() << "\n";
+            return 1;
+        }
+        return 0;
+    }
+    if (mode == "batch" && argc >= 5) {
+        const int B = atoi(argv[2]);
+        const uint64_t n = strtoull(argv[3], nullptr, 10);
+        const double p = atof(argv[4]);
+        const uint64_t mask = argc > 5 ? strtoull(argv[5], nullptr, 0) : 0;
+        try {
+            std::vector<std::vector<std::string>> problems;
+            for (int k = 0; k < B; ++k) problems.push_back(generate(2, n / (uint64_t)(k + 1), p, 12345 + (uint64_t)k));
+            std::unique_ptr<mums::MemHash> mh;
+            if (mask) {
+                auto* m = new mums::MaskedMemHash(0);
+                m->SetMask(mask);
+                mh.reset(m);
+            } else {
+                mh.reset(new mums::MemHash(0));
+            }
+            std::vector<mums::MatchList> lists;
+            mh->FindMatchesBatch(problems, lists);
+            std::ostringstream os;
+            for (int k = 0; k < B; ++k) {
+                os << "# problem " << k << '\n';
+                for (const auto& m : lists[k]) os << m << '\n';
+            }
+            os << "== loop\n";
+            uint64_t probes = 0;
+            for (uint64_t v : mh->BatchInfo().probes) probes += v;
+            for (int k = 0; k < B; ++k) {
+                os << "# problem " << k << '\n';
+                const uint32_t w = mums_default_seed_weight((problems[k][0].size() + problems[k][1].size()) / 2);
+                if (!w) continue;
+                mh->Clear();
+                mh->SetSeed((uint64_t)mums_get_seed((int)w, 0));
+                mums::MatchList ml;
+                ml.seq_table = problems[k];
+                mh->FindMatches(ml);
+                for (const auto& m : ml) os << m << '\n';
+            }
+            std::cout << os.str();
+            std::cerr << "problems " << B << " probes " << probes << "\n";
         } catch (const std::exception& e) {
             std::cerr << "error: " << e.what() << "\n";
             return 1;
