@@ -23,8 +23,13 @@
 // A line-hash collision whose two lines interleave in x order splits a chain into two
 // segments with the same extended entry, and the replay then sees it twice: with a 16-bit
 // hash the 4 x 10 Mbp related known answer gains 4 matches (MUMS_LINE_HASH_BITS A/B,
-// round 4).  32 bits: only colliding multi-probe lines whose x ranges overlap do this --
-// none in the test corpus or the C3 known answer; the residual risk is noted in DESIGN.md.
+// round 4).  32 bits: only colliding multi-probe lines whose x ranges overlap do this.  The
+// rearranged corpus (tests/rearranged_inputs.py: up to 6 108 lines per MatchList, tens of
+// thousands of probe lines per find) and the C3 known answer give the oracle's lists in the
+// hashed order and in the exact one alike, which shows the order, links and segment scan right
+// across many short runs.  No interleaved colliding pair of lines is known in it, so the
+// retry after a detected collision (launch_chains) is still reached only through
+// MUMS_DEV_LINE_EXACT, which forces the exact order; the residual risk is noted in DESIGN.md.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>

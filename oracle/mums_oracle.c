@@ -701,16 +701,23 @@ static void enumerate_matches(memhash_t* h, const oracle_params* prm, const idme
 }
 
 /* PairwiseMatchFinder::EnumerateMatches (PairwiseMatchFinder.cpp:37-73): the group   */
-/* sorted by genome id (std::list::sort, stable; grp is genome-major already), the     */
-/* genomes occurring exactly once kept in order, then MemHash::HashMatch of every pair  */
-/* (a before b).  HashMatch always returns true, so the && chain never short-circuits.  */
+/* sorted by genome id (match_list.sort(&idmer_id_lessthan), :39), the genomes occurring */
+/* exactly once kept in that order, then MemHash::HashMatch of every pair (a before b).  */
+/* HashMatch always returns true, so the && chain never short-circuits.  grp holds one   */
+/* run per genome, but in the merge's arrival order (a head re-inserted into cur_mers    */
+/* goes in front of the equal keys), not by id: the single-copy records are sorted here. */
+/* The table does not depend on the order of one group's calls, the match log does.      */
 static void enumerate_pairwise(memhash_t* h, const oracle_params* prm, const idmer_t* grp, int cnt, idmer_t* uniq,
                                int64_t* scratch) {
     int nu = 0;
     for (int a = 0; a < cnt;) {
         int b = a + 1;
         while (b < cnt && grp[b].g == grp[a].g) ++b;
-        if (b - a == 1) uniq[nu++] = grp[a];
+        if (b - a == 1) {
+            int at = nu++;
+            while (at > 0 && uniq[at - 1].g > grp[a].g) { uniq[at] = uniq[at - 1]; --at; }
+            uniq[at] = grp[a];
+        }
         a = b;
     }
     for (int a = 0; a < nu; ++a)

@@ -1,5 +1,5 @@
 """Writes eo_v2_cases.json: for every run of tests/test_eliminate_overlaps_v2_cpu.py (each case x
-eliminate_both, the subset runs, and FindMatches -> EliminateOverlaps_v2 -> LengthFilter on the
+eliminate_both, the subset runs, the edge lists, and FindMatches -> EliminateOverlaps_v2 -> LengthFilter on the
 repeat-rich input) the output count and the md5 of lengths (<u8) + starts (<i8), recorded from
 the C++ model tests/eo2_model.cpp.  Needs g++ and the built oracle:
 
@@ -22,7 +22,7 @@ def main():
         oracle.build()
     L = t.load_model()
     runs = {}
-    inputs = {c: t.v2_matchlist(*c) for c in t.CASES}
+    inputs = t.all_inputs()
     for key, c, ids, both in t.fixture_runs():
         ol, os_, cnt = t.model_eo2(L, *inputs[c], ids, both)
         runs[key] = {"count": len(ol), "md5": t.digest(ol, os_)}

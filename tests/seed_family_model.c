@@ -9,13 +9,15 @@
  * keys and the extension context are rebuilt per round (as in oracle_find_matches).
  *
  * PairwiseMatchFinder rounds: the reference sorts a seed group by sequence id before it hashes
- * the pairs (match_list.sort(&idmer_id_lessthan), PairwiseMatchFinder.cpp:39), the oracle's
- * enumerate_pairwise keeps the merge's run order.  The table does not depend on the order of
- * one group's calls (their pairs differ in the sequences present), the match log does.  So such
+ * the pairs (match_list.sort(&idmer_id_lessthan), PairwiseMatchFinder.cpp:39).  The table does
+ * not depend on the order of one group's calls (their pairs differ in the sequences present),
+ * the match log does.  The oracle's enumerate_pairwise once kept the merge's run order, so such
  * a round first records the oracle's AddHashEntry calls (its record mode), puts every group's
  * calls in the reference's order -- by (first, second) sequence of the pair; a group's calls are
  * consecutive and linked by a shared (sequence, position), which no two groups share -- and then
- * makes the calls.
+ * makes the calls.  The oracle sorts by sequence id itself now (tests/test_gpu_rearranged.py found
+ * its match log out of order on rearranged genomes); the reordering here is kept as a second,
+ * independent statement of the order and changes nothing.
  */
 #include "../oracle/mums_oracle.c"
 

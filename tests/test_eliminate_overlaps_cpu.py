@@ -68,6 +68,48 @@ def random_matchlist(rng, M, G, n=20000, max_len=300, p_absent=0.3, p_rev=0.3, s
     return lengths, starts
 
 
+EO_TILE = 1024   # overlaps.hip kEoTile: heads_kernel's tiles, tile_prefix_kernel's max-scan over them
+
+
+def carried_head_matchlist(M=20000, G=3, span=2_000_000, seed=21, left=300_000, length=400_000):
+    """random_matchlist (every length below 300: the running maximum of the ends always comes
+    from the neighbouring entries) plus one match defined in every genome that spans several
+    tiles of the sorted order: behind it only the tile prefix carries the cluster on."""
+    rng = np.random.default_rng(seed)
+    lengths, starts = random_matchlist(rng, M, G, start_span=span)
+    big = np.array([[left + 17 * g for g in range(G)]], dtype=np.int64)
+    return np.concatenate([lengths, np.array([length], dtype=np.uint64)]), np.concatenate([starts, big])
+
+
+def above_2p32_matchlist(M=3000, G=4, span=30000, seed=22, shift=5_000_000_000):
+    """random_matchlist with 5e9 added to every forward start and subtracted from every reverse
+    one: coordinates and ends that do not fit 32 bits."""
+    rng = np.random.default_rng(seed)
+    lengths, starts = random_matchlist(rng, M, G, start_span=span)
+    return lengths, starts + np.sign(starts) * shift
+
+
+EDGE_LISTS = {"carried_head": carried_head_matchlist, "above_2p32": above_2p32_matchlist}
+SORT_ORDERS = ("ascending", "descending", "organ_pipe", "sawtooth16", "all_equal_but_one")
+SORT_SIZES = (17, 1000, 65536)
+
+
+def adversarial_keys(order, n):
+    """Key orders that drive introsort's median-of-three / depth limit differently from random keys."""
+    i = np.arange(n, dtype=np.uint64)
+    if order == "ascending":
+        return i + 1
+    if order == "descending":
+        return n - i
+    if order == "organ_pipe":
+        return np.minimum(i, n - 1 - i) + 1
+    if order == "sawtooth16":
+        return i % 16 + 1
+    keys = np.full(n, 7, dtype=np.uint64)
+    keys[n // 2] = 3
+    return keys
+
+
 def model_eo(L, lengths, starts):
     M, G = starts.shape
     cap = 8 * M + 64
@@ -100,3 +142,43 @@ def test_eliminate_overlaps_on_findmatches_output(model):
     ml, ms = model_eo(model, lengths, starts)
     assert len(ol) != len(lengths) or not np.array_equal(os_, starts)   # something was cropped
     assert np.array_equal(ol, ml) and np.array_equal(os_, ms)
+
+
+def test_carried_head_precondition():
+    """In pass 0's sort order (LeftEnd in sequence 0) the long match alone carries the running
+    maximum of the ends across at least 3 tile boundaries: behind each of them lies an entry that
+    starts before the long match ends but at or after every other earlier end (a cluster head
+    without it), and for one boundary the long match is not even in the previous tile."""
+    lengths, starts = carried_head_matchlist()
+    k = np.abs(starts[:, 0]).astype(np.uint64)
+    assert (k != 0).all()
+    order = oracle.std_sort_ids(k)
+    K = k[order].astype(np.int64)
+    ends = K + lengths[order].astype(np.int64)
+    pos = int(np.nonzero(order == len(k) - 1)[0][0])
+    others = ends.copy()
+    others[pos] = 0
+    run_wo = np.concatenate([[0], np.maximum.accumulate(others)[:-1]])   # exclusive, without the long match
+    idx = np.arange(len(K))
+    alone = (idx > pos) & (K < ends[pos]) & (K >= run_wo)
+    tiles = sorted({int(t) for t in idx[alone] // EO_TILE if t * EO_TILE > pos})
+    assert len(tiles) >= 3, tiles
+    assert max(tiles) >= pos // EO_TILE + 2
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_LISTS))
+def test_eliminate_overlaps_edge_lists(model, name):
+    lengths, starts = EDGE_LISTS[name]()
+    ol, os_ = oracle.eliminate_overlaps(lengths, starts)
+    ml, ms = model_eo(model, lengths, starts)
+    assert len(ol) != len(lengths) or not np.array_equal(os_, starts)
+    assert np.array_equal(ol, ml) and np.array_equal(os_, ms)
+    if name == "above_2p32":
+        assert (np.abs(os_[os_ != 0]) > 1 << 32).all()
+
+
+@pytest.mark.parametrize("n", SORT_SIZES)
+@pytest.mark.parametrize("order", SORT_ORDERS)
+def test_std_sort_restatement_adversarial_orders(model, order, n):
+    keys = adversarial_keys(order, n)
+    assert np.array_equal(oracle.std_sort_ids(keys), model_sort(model, keys))

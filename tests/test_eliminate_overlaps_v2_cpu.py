@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle
-from test_eliminate_overlaps_cpu import random_matchlist
+from test_eliminate_overlaps_cpu import EDGE_LISTS, random_matchlist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "tests", "_build")
@@ -95,6 +95,21 @@ def digest(lengths, starts):
     return hashlib.md5(np.asarray(lengths).astype("<u8").tobytes() + np.asarray(starts).astype("<i8").tobytes()).hexdigest()
 
 
+def build_input(case):
+    """The MatchList of a run: v2_matchlist of a CASES tuple, or an edge list of
+    test_eliminate_overlaps_cpu.py by name (a cluster head carried across tiles, coordinates
+    above 2^32), taken as it is."""
+    return EDGE_LISTS[case]() if isinstance(case, str) else v2_matchlist(*case)
+
+
+def all_inputs():
+    return {c: build_input(c) for c in list(CASES) + sorted(EDGE_LISTS)}
+
+
+def edge_key(name, eliminate_both):
+    return f"edge_{name}_both{int(eliminate_both)}_idsall"
+
+
 def case_key(M, G, span, seed, eliminate_both, seq_ids=None):
     ids = "all" if seq_ids is None else "-".join(str(i) for i in seq_ids)
     return f"M{M}_G{G}_span{span}_seed{seed}_both{int(eliminate_both)}_ids{ids}"
@@ -117,6 +132,9 @@ def fixture_runs():
     for ids in ([G - 1, 0], [0, 0]):
         for both in (False, True):
             runs.append((case_key(*SUBSET_CASE, both, ids), SUBSET_CASE, ids, both))
+    for name in sorted(EDGE_LISTS):
+        for both in (False, True):
+            runs.append((edge_key(name, both), name, None, both))
     return runs
 
 
@@ -128,7 +146,7 @@ def recorded():
 
 @pytest.fixture(scope="module")
 def inputs():
-    return {c: v2_matchlist(*c) for c in CASES}
+    return all_inputs()
 
 
 @pytest.fixture(scope="module")
@@ -150,6 +168,15 @@ def test_no_new_match_is_kept(results, inputs, key, case, ids, both):
     ol, _, cnt = results[key]
     assert cnt["kept"] == 0
     assert len(ol) <= len(inputs[case][0])
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_LISTS))
+@pytest.mark.parametrize("both", [False, True])
+def test_edge_lists_have_work(results, inputs, name, both):
+    ol, os_, cnt = results[edge_key(name, both)]
+    lengths, starts = inputs[name]
+    assert cnt["pairs"] > 0 and cnt["del_i"] + cnt["del_j"] + cnt["crop_i"] + cnt["crop_j"] > 0
+    assert len(ol) < len(lengths) or not np.array_equal(os_, starts)
 
 
 def test_v2_is_not_v1(results, inputs):

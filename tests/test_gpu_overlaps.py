@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from test_eliminate_overlaps_cpu import random_matchlist
+from test_eliminate_overlaps_cpu import EDGE_LISTS, SORT_ORDERS, SORT_SIZES, adversarial_keys, random_matchlist
 
 pytestmark = pytest.mark.gpu
 
@@ -40,6 +40,17 @@ def test_std_sort_replay_depth_limit(gpu_lib, oracle_mod, depth, n):
     assert np.array_equal(got, oracle_mod.std_sort_ids(keys, depth))
 
 
+@pytest.mark.parametrize("n", SORT_SIZES)
+@pytest.mark.parametrize("order", SORT_ORDERS)
+def test_std_sort_replay_adversarial_orders(gpu_lib, oracle_mod, order, n):
+    """Sorted, reversed, organ-pipe, sawtooth and all-equal-but-one keys (the restatement itself
+    against the real std::sort: test_eliminate_overlaps_cpu.py)."""
+    keys = adversarial_keys(order, n)
+    with gpu_lib.MemHash(0) as mh:
+        got = mh._debug_std_sort(keys)
+    assert np.array_equal(got, oracle_mod.std_sort_ids(keys))
+
+
 def eo_both(gpu_lib, oracle_mod, lengths, starts):
     ml = gpu_lib.MatchList(np.asarray(lengths, dtype=np.uint64), np.asarray(starts, dtype=np.int64))
     got = gpu_lib.EliminateOverlaps(ml)
@@ -53,6 +64,17 @@ def eo_both(gpu_lib, oracle_mod, lengths, starts):
 def test_eliminate_overlaps_random(gpu_lib, oracle_mod, M, G, span, seed):
     rng = np.random.default_rng(seed)
     lengths, starts = random_matchlist(rng, M, G, start_span=span)
+    got, rl, rs = eo_both(gpu_lib, oracle_mod, lengths, starts)
+    assert len(got) == len(rl)
+    assert np.array_equal(got.lengths, rl) and np.array_equal(got.starts, rs)
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_LISTS))
+def test_eliminate_overlaps_edge_lists(gpu_lib, oracle_mod, name):
+    """A cluster head carried across several 1024-entry tiles by one long match (the tile
+    prefix of heads_kernel; test_carried_head_precondition on the CPU side) and coordinates
+    above 2^32."""
+    lengths, starts = EDGE_LISTS[name]()
     got, rl, rs = eo_both(gpu_lib, oracle_mod, lengths, starts)
     assert len(got) == len(rl)
     assert np.array_equal(got.lengths, rl) and np.array_equal(got.starts, rs)

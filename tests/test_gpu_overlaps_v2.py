@@ -30,7 +30,7 @@ def live_model():
 
 @pytest.fixture(scope="module")
 def inputs():
-    return {c: cpu.v2_matchlist(*c) for c in cpu.CASES}
+    return cpu.all_inputs()
 
 
 def check(got, recorded_run, live_model, lengths, starts, ids, both):
