@@ -297,6 +297,42 @@ int  mums_find_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const char* ascii, c
  * MemCollisionCount (MemHash.h:97), restarts[B] = MER_REPEAT_LIMIT restarts of problem p; any of
  * the four may be NULL.  MUMS_E_INVALID when the context holds no batch result. */
 int  mums_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* probes, uint64_t* collisions, uint64_t* restarts);
+/* The whole body of ProgressiveAligner::pairwiseAnchorSearch (ProgressiveAligner.cpp:589-678) for B
+ * problems in one call, from host ASCII to the final per-problem anchor lists.  Sequences as in
+ * mums_find_batch (seq_off: B*G+1 entries).  The call starts as MemHash::Clear does; then for round
+ * r = 0 .. rounds-1 every problem runs ClearSequences + FindMatches with seed patterns[r] into its
+ * own hash table (the seed family of --seed-family, :619-653; rounds 1..8, every pattern != 0, else
+ * MUMS_E_INVALID; patterns may repeat, their lengths may differ).  Table size and MaskedMemHash
+ * mask: the context's; its own seed pattern is neither read nor changed.  After the last round each
+ * problem's table in GetMatchList order goes through EliminateOverlaps_v2(list, eliminate_both)
+ * (the two-argument overload, ProgressiveAligner.h:397-406: every sequence in order) and then
+ * LengthFilter(min_length) (MatchList.h:652-664: keeps Length() >= min_length; 0 keeps everything).
+ * Problem p's part of the result is bit for bit what Clear; per round ClearSequences, mums_set_seed,
+ * the sequences, mums_find; mums_eliminate_overlaps_v2(NULL, 0, eliminate_both); mums_length_filter
+ * give for p alone.  Starts are 1-based in p's own sequences; the translation to genome coordinates
+ * (:661-670) is the caller's.
+ * Result and state afterwards as after mums_find_batch: one MatchList, the problems' lists in
+ * problem order (seq_count = G), the same calls refused with MUMS_E_UNSUPPORTED; mums_clear,
+ * mums_find, mums_find_batch and mums_load_matches end that state.  mums_get_stats: sums over
+ * problems and rounds (mem_count = table entries before the tail; ms_keys / ms_sort / ms_replay over
+ * all rounds, ms_output = the tail and the emit).  mums_batch_info answers for this result too.
+ * Limits, refusals ('-' -> MUMS_E_GAP naming the problem, modes, G 2..64, B == 0) as mums_find_batch;
+ * the seed-mers of each round of one batch must stay below 2^32.  Problems run alone inside the
+ * call as there (cap, MER_REPEAT_LIMIT, the largest of a batch), with their tail. */
+int  mums_anchor_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const char* ascii, const uint64_t* seq_off,
+                       const uint64_t* patterns, uint32_t rounds, int eliminate_both, uint64_t min_length);
+/* The same tail on the caller's lists (from mums_find_batch, a file, ...): list p = rows
+ * [match_off[p], match_off[p+1]) of lengths / starts (G signed starts per row, NO_MATCH = 0, as in
+ * mums_load_matches).  Result and state as after mums_anchor_batch.  A list of more than 1024 rows
+ * runs through the single-list path inside the call (the same result). */
+int  mums_anchor_tail_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const uint64_t* match_off,
+                            const uint64_t* lengths, const int64_t* starts, int eliminate_both, uint64_t min_length);
+/* After mums_anchor_batch or mums_anchor_tail_batch: match_off[B+1] = the final lists' rows,
+ * table_entries[B] = MemCount before the tail (for the tail call: the input row counts), probes,
+ * collisions, restarts [B] over all rounds (0 for the tail call).  Any pointer may be NULL.
+ * MUMS_E_INVALID when the context holds no such result. */
+int  mums_anchor_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* table_entries, uint64_t* probes,
+                            uint64_t* collisions, uint64_t* restarts);
 /* Test entry point: ids[0..n) = the permutation libstdc++ std::sort leaves on keys with
  * operator< (depth_override >= 0 forces the introsort depth limit; -1 = 2*lg(n)). */
 int  mums_debug_std_sort(mums_ctx* ctx, const uint64_t* keys, uint64_t n, int depth_override, uint32_t* ids);

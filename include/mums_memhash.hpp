@@ -338,6 +338,94 @@ public:
         }
     }
     const BatchCounters& BatchInfo() const { return batch_; }
+    // Per-problem counters of the last AnchorSearchBatch / AnchorTailBatch (mums_anchor_batch_info):
+    // table_entries = MemCount before the tail (the input rows of a tail call)
+    struct AnchorCounters {
+        std::vector<uint64_t> table_entries, probes, collisions, restarts;
+    };
+    // ProgressiveAligner::pairwiseAnchorSearch (ProgressiveAligner.cpp:589-678) for many gap problems
+    // in one device pass per seed weight (mums_anchor_batch): per problem Clear; for the seed ranks
+    // 0, 1, 2 of its weight (rank 0 alone without seed_families) ClearSequences + FindMatches into one
+    // table; EliminateOverlaps_v2(list, eliminate_both); LengthFilter(min_length).  weights empty:
+    // getDefaultSeedWeight(mean length) per problem (:615-616); a weight of 0 gives an empty list and
+    // no search (:626-633).  out[p]: starts in problem p's own sequences (the translation of :661-670
+    // is the caller's).  The object's own seed is not changed.
+    virtual void AnchorSearchBatch(const std::vector<std::vector<std::string>>& problems, std::vector<MatchList>& out,
+                                   bool seed_families = true, const std::vector<uint32_t>& weights = {},
+                                   bool eliminate_both = false, uint64_t min_length = 12) {
+        const size_t B = problems.size();
+        if (!weights.empty() && weights.size() != B) throw InvalidData("AnchorSearchBatch: one seed weight per problem");
+        const size_t G = B ? problems[0].size() : 2;
+        out.assign(B, MatchList());
+        anchor_ = AnchorCounters();
+        anchor_.table_entries.assign(B, 0);
+        anchor_.probes.assign(B, 0);
+        anchor_.collisions.assign(B, 0);
+        anchor_.restarts.assign(B, 0);
+        std::vector<uint32_t> ws;        // distinct weights in order of first appearance
+        std::vector<std::vector<size_t>> members;
+        for (size_t p = 0; p < B; ++p) {
+            if (problems[p].size() != G) throw InvalidData("AnchorSearchBatch: every problem needs the same sequence count");
+            uint32_t w = 0;
+            if (!weights.empty()) {
+                w = weights[p];
+            } else {
+                uint64_t total = 0;
+                for (const std::string& s : problems[p]) total += s.size();
+                w = mums_default_seed_weight(G ? total / G : 0);
+            }
+            if (w == 0) continue;
+            size_t k = 0;
+            while (k < ws.size() && ws[k] != w) ++k;
+            if (k == ws.size()) { ws.push_back(w); members.emplace_back(); }
+            members[k].push_back(p);
+        }
+        if (ws.empty()) check(mums_clear(ctx_));
+        for (size_t k = 0; k < ws.size(); ++k) {
+            const std::vector<size_t>& idx = members[k];
+            std::string blob;
+            std::vector<uint64_t> off(1, 0);
+            for (size_t p : idx)
+                for (const std::string& s : problems[p]) {
+                    blob += s;
+                    off.push_back(blob.size());
+                }
+            std::vector<uint64_t> pats;
+            for (int r = 0; r < (seed_families ? 3 : 1); ++r) pats.push_back((uint64_t)mums_get_seed((int)ws[k], r));
+            check(mums_anchor_batch(ctx_, (uint32_t)idx.size(), (uint32_t)G, blob.data(), off.data(), pats.data(),
+                                    (uint32_t)pats.size(), eliminate_both ? 1 : 0, min_length));
+            anchor_collect(idx, out);
+        }
+    }
+    // pairwiseAnchorSearch's tail on the caller's lists in one device pass (mums_anchor_tail_batch):
+    // EliminateOverlaps_v2(list, eliminate_both) over every sequence, then LengthFilter(min_length),
+    // each list on its own; seq_count sequences per match in every list.
+    virtual void AnchorTailBatch(const std::vector<MatchList>& lists, uint32_t seq_count, std::vector<MatchList>& out,
+                                 bool eliminate_both = false, uint64_t min_length = 12) {
+        const size_t B = lists.size();
+        std::vector<uint64_t> off(1, 0), len;
+        std::vector<int64_t> st;
+        for (const MatchList& ml : lists) {
+            for (const Match& m : ml) {
+                if (m.starts.size() != seq_count) throw InvalidData("AnchorTailBatch: a match with another sequence count");
+                len.push_back(m.length);
+                st.insert(st.end(), m.starts.begin(), m.starts.end());
+            }
+            off.push_back(len.size());
+        }
+        check(mums_anchor_tail_batch(ctx_, (uint32_t)B, seq_count, off.data(), len.data(), st.data(), eliminate_both ? 1 : 0,
+                                     min_length));
+        out.assign(B, MatchList());
+        anchor_ = AnchorCounters();
+        anchor_.table_entries.assign(B, 0);
+        anchor_.probes.assign(B, 0);
+        anchor_.collisions.assign(B, 0);
+        anchor_.restarts.assign(B, 0);
+        std::vector<size_t> idx(B);
+        for (size_t p = 0; p < B; ++p) idx[p] = p;
+        anchor_collect(idx, out);
+    }
+    const AnchorCounters& AnchorBatchInfo() const { return anchor_; }
     // MemHash::CreateMatches (MemHash.cpp:104-107)
     virtual bool CreateMatches() {
         check(mums_find(ctx_));
@@ -526,6 +614,21 @@ protected:
     int device_ = 0;
     uint32_t repeat_tol_ = 0, enum_tol_ = 1, table_size_ = 40000;
     BatchCounters batch_;
+    AnchorCounters anchor_;
+    // the context's anchor batch result -> the lists and counters of the problems idx
+    void anchor_collect(const std::vector<size_t>& idx, std::vector<MatchList>& out) {
+        MatchList all;
+        GetMatchList(all);
+        std::vector<uint64_t> mo(idx.size() + 1), te(idx.size()), pr(idx.size()), co(idx.size()), rs(idx.size());
+        check(mums_anchor_batch_info(ctx_, mo.data(), te.data(), pr.data(), co.data(), rs.data()));
+        for (size_t j = 0; j < idx.size(); ++j) {
+            out[idx[j]].assign(all.begin() + mo[j], all.begin() + mo[j + 1]);
+            anchor_.table_entries[idx[j]] = te[j];
+            anchor_.probes[idx[j]] = pr[j];
+            anchor_.collisions[idx[j]] = co[j];
+            anchor_.restarts[idx[j]] = rs[j];
+        }
+    }
 };
 
 // MaskedMemHash (MaskedMemHash.h:25-40)

@@ -111,7 +111,7 @@ EXPORTED_SYMBOLS = [
     "mums_genome_device", "mums_shard_chain_label", "mums_shard_chain_export", "mums_shard_find_labelled",
     "mums_shard_chain_info", "mums_shard_chain_entries", "mums_shard_entry_thresholds", "mums_shard_kept_export",
     "mums_shard_find_kept", "mums_comm_exchange_info", "mums_eliminate_overlaps_v2", "mums_clear_sequences",
-    "mums_find_batch", "mums_batch_info",
+    "mums_find_batch", "mums_batch_info", "mums_anchor_batch", "mums_anchor_tail_batch", "mums_anchor_batch_info",
 ]
 
 # mums_comm_ops (include/mums.h): the caller's transport as two host callbacks
@@ -238,6 +238,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mums_match_log_copy.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     lib.mums_find_batch.argtypes = [vp, u32, u32, vp, vp]
     lib.mums_batch_info.argtypes = [vp, vp, vp, vp, vp]
+    lib.mums_anchor_batch.argtypes = [vp, u32, u32, vp, vp, vp, u32, i32, u64]
+    lib.mums_anchor_tail_batch.argtypes = [vp, u32, u32, vp, vp, vp, i32, u64]
+    lib.mums_anchor_batch_info.argtypes = [vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -290,6 +293,30 @@ def batch_seed_groups(problems: Sequence[Sequence[bytes]], seeds: Optional[Seque
         if pat:
             groups.setdefault(pat, []).append(p)
     return patterns, groups
+
+
+def anchor_seed_groups(problems: Sequence[Sequence[bytes]], seed_families: bool = True, weights=None,
+                       default_weight=None, get_seed=None):
+    """The grouping of MemHash.AnchorSearchBatch, host logic only: (weights, groups, patterns).
+    weights[p] = problem p's seed weight: weights[p] when given, else getDefaultSeedWeight(mean
+    length) as pairwiseAnchorSearch chooses it (ProgressiveAligner.cpp:615-616); 0 means no search
+    (the early return at :626-633).  groups = {weight: [problem indices in order]} for the weights
+    != 0 in order of first appearance; patterns[weight] = getSeed(weight, rank) for the ranks 0, 1, 2
+    of a seed family (:619-653), or rank 0 alone."""
+    default_weight = default_weight or getDefaultSeedWeight
+    get_seed = get_seed or getSeed
+    if weights is not None and len(weights) != len(problems):
+        raise ValueError("AnchorSearchBatch: one seed weight per problem")
+    ws: List[int] = []
+    groups: dict = {}
+    for p, prob in enumerate(problems):
+        w = int(weights[p]) if weights is not None else int(default_weight(sum(len(s) for s in prob) // max(len(prob), 1)))
+        ws.append(w)
+        if w:
+            groups.setdefault(w, []).append(p)
+    ranks = (0, 1, 2) if seed_families else (0,)
+    patterns = {w: [get_seed(w, r) for r in ranks] for w in groups}
+    return ws, groups, patterns
 
 
 @dataclass
@@ -486,6 +513,88 @@ class MemHash:
         if getattr(self, "_batch_info", None) is None:
             raise MumsError(MUMS_E_INVALID, "no FindMatchesBatch on this object")
         return self._batch_info
+
+    def _anchor_collect(self, idx, G, out, info) -> None:
+        """The context's anchor batch result -> the lists and counters of the problems idx."""
+        ml = self.GetMatchList()
+        n = len(idx)
+        mo = np.zeros(n + 1, dtype=np.uint64)
+        te, pr, co, rs = (np.zeros(n, dtype=np.uint64) for _ in range(4))
+        self._check(self._lib.mums_anchor_batch_info(self._ctx, mo.ctypes.data, te.ctypes.data, pr.ctypes.data,
+                                                     co.ctypes.data, rs.ctypes.data))
+        for k, p in enumerate(idx):
+            a, b = int(mo[k]), int(mo[k + 1])
+            out[p] = MatchList(ml.lengths[a:b].copy(), ml.starts[a:b].copy().reshape(b - a, G))
+            info["matches"][p] = b - a
+            info["table_entries"][p], info["probes"][p], info["collisions"][p], info["restarts"][p] = te[k], pr[k], co[k], rs[k]
+
+    def AnchorSearchBatch(self, problems: Sequence[Sequence[bytes]], seed_families: bool = True, weights=None,
+                          eliminate_both: bool = False, min_length: int = 12) -> List[MatchList]:
+        """ProgressiveAligner::pairwiseAnchorSearch (ProgressiveAligner.cpp:589-678) for many gap
+        problems in one device pass per seed weight (mums_anchor_batch): per problem Clear; for the
+        seed ranks 0, 1, 2 of its weight (rank 0 alone without seed_families) ClearSequences +
+        FindMatches into one table; EliminateOverlaps_v2(list, eliminate_both); LengthFilter(
+        min_length) (MIN_ANCHOR_LENGTH + 3 = 12, :659).  problems: G-tuples of bytes, the same G for
+        all; weights=None: getDefaultSeedWeight(mean length) per problem, a problem of weight 0 gets
+        an empty list and no device work (:626-633).  Returns one MatchList per problem with starts
+        in the problem's own sequences (the translation of :661-670 is the caller's);
+        AnchorBatchInfo() has every problem's counters.  The object's own seed is not changed."""
+        problems = [tuple(s.encode() if isinstance(s, str) else bytes(s) for s in prob) for prob in problems]
+        B = len(problems)
+        G = len(problems[0]) if B else 2
+        if any(len(prob) != G for prob in problems):
+            raise ValueError("AnchorSearchBatch: every problem needs the same number of sequences")
+        ws, groups, patterns = anchor_seed_groups(problems, seed_families, weights)
+        out: List[Optional[MatchList]] = [None] * B
+        info = {k: np.zeros(B, dtype=np.uint64) for k in ("matches", "table_entries", "probes", "collisions", "restarts")}
+        self._keepalive.clear()
+        for p in range(B):
+            if ws[p] == 0:
+                out[p] = MatchList(np.zeros(0, dtype=np.uint64), np.zeros((0, G), dtype=np.int64))
+        if not groups:
+            self._check(self._lib.mums_clear(self._ctx))
+        for w, idx in groups.items():
+            blob = b"".join(s for p in idx for s in problems[p])
+            off = np.zeros(len(idx) * G + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(s) for p in idx for s in problems[p]], dtype=np.uint64)
+            pats = np.asarray(patterns[w], dtype=np.uint64)
+            self._check(self._lib.mums_anchor_batch(self._ctx, len(idx), G, blob, off.ctypes.data, pats.ctypes.data,
+                                                    len(pats), int(bool(eliminate_both)), int(min_length)))
+            self._anchor_collect(idx, G, out, info)
+        self._anchor_info = info
+        return out  # type: ignore[return-value]
+
+    def AnchorTailBatch(self, lists: Sequence["MatchList"], eliminate_both: bool = False, min_length: int = 12) -> List[MatchList]:
+        """pairwiseAnchorSearch's tail on the caller's lists in one device pass (mums_anchor_tail_batch):
+        EliminateOverlaps_v2(list, eliminate_both) over every sequence, then LengthFilter(min_length),
+        each list on its own.  Every list needs the same number of sequences."""
+        B = len(lists)
+        shapes = {int(np.asarray(ml.starts).shape[1]) for ml in lists if np.asarray(ml.starts).ndim == 2}
+        if len(shapes) > 1:
+            raise ValueError("AnchorTailBatch: every list needs the same number of sequences")
+        G = shapes.pop() if shapes else 2
+        rows =[np.ascontiguousarray(ml.starts, dtype=np.int64).reshape(len(ml), G) for ml in lists]
+        lengths = np.ascontiguousarray(np.concatenate([np.asarray(ml.lengths, dtype=np.uint64) for ml in lists])
+                                       if B else np.zeros(0, dtype=np.uint64))
+        starts = np.ascontiguousarray(np.concatenate(rows) if B else np.zeros((0, G), dtype=np.int64))
+        off = np.zeros(B + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(ml) for ml in lists], dtype=np.uint64)
+        self._keepalive.clear()
+        self._check(self._lib.mums_anchor_tail_batch(self._ctx, B, G, off.ctypes.data, lengths.ctypes.data,
+                                                     starts.ctypes.data, int(bool(eliminate_both)), int(min_length)))
+        out: List[Optional[MatchList]] = [None] * B
+        info = {k: np.zeros(B, dtype=np.uint64) for k in ("matches", "table_entries", "probes", "collisions", "restarts")}
+        self._anchor_collect(list(range(B)), G, out, info)
+        self._anchor_info = info
+        return out  # type: ignore[return-value]
+
+    def AnchorBatchInfo(self) -> dict:
+        """Per problem of the last AnchorSearchBatch / AnchorTailBatch: matches (final rows),
+        table_entries (MemCount before the tail; the input rows of a tail call), probes, collisions
+        and restarts over all rounds, as uint64 arrays."""
+        if getattr(self, "_anchor_info", None) is None:
+            raise MumsError(MUMS_E_INVALID, "no AnchorSearchBatch on this object")
+        return self._anchor_info
 
     def CreateMatches(self) -> bool:
         """MemHash::CreateMatches (MemHash.cpp:104-107)."""
@@ -959,5 +1068,5 @@ class PairwiseMatchFinder(MemHash):
 __all__ = [
     "MemHash", "MaskedMemHash", "ParallelMemHash", "PairwiseMatchFinder", "MatchList", "MumsError", "GapInSequence", "getSeed", "getSeedLength",
     "getSeedWeight", "getDefaultSeedWeight", "load_library", "EXPORTED_SYMBOLS", "STAGE_SEEDS", "STAGE_ALL", "ShardedMemHash",
-    "shard_key_ranges", "EliminateOverlaps", "EliminateOverlaps_v2", "batch_seed_groups",
+    "shard_key_ranges", "EliminateOverlaps", "EliminateOverlaps_v2", "batch_seed_groups", "anchor_seed_groups",
 ]

@@ -286,10 +286,16 @@ struct BatchReplayArgs {
     uint32_t table_size;
     int masked;
     uint64_t seq_mask;
+    const uint32_t* ord_base;   // CARRY: problem p's slice of ord and its capacity
+    const uint32_t* ord_cap;
 };
 
-template <int MG>
-__global__ __launch_bounds__(kBatchBlock) void batch_replay_kernel(BatchReplayArgs a) {
+// CARRY (mums_anchor_batch): one round of a seed family.  The lane goes on from the
+// table the rounds before left in its slice (MemHash::ClearSequences keeps the table,
+// ProgressiveAligner.cpp:619-653): AddHashEntry's search below already is the keep rule, the stored
+// entries compare with mer = 0 and the probes with this round's L.
+template <int MG, bool CARRY>
+__device__ __forceinline__ void batch_replay_lane(const BatchReplayArgs& a) {
     const uint32_t t = blockIdx.x * kBatchBlock + threadIdx.x;
     if (t >= a.B) return;
     const uint32_t p = a.order[t];
@@ -297,11 +303,17 @@ __global__ __launch_bounds__(kBatchBlock) void batch_replay_kernel(BatchReplayAr
     const uint32_t* mb = a.mbase + (uint64_t)p * a.G;
     const BatchSeg q{mb, a.nlen + (uint64_t)p * a.G};
     const uint32_t r0 = mb[0], r1 = mb[G];
-    uint64_t* ord = a.ord + (r0 >> 1);
-    const uint32_t ord_cap = (r1 - r0) >> 1;   // one entry needs a probe, a probe two records
+    uint64_t* ord = a.ord + (CARRY ? a.ord_base[p] : (r0 >> 1));
+    const uint32_t ord_cap = CARRY ? a.ord_cap[p] : (r1 - r0) >> 1;   // one entry needs a probe, a probe two records
     const uint64_t stride = (uint64_t)(G + 2);
     const int64_t T = (int64_t)a.table_size;
     uint32_t n = 0, probes = 0, coll = 0, flag = 0;
+    if (CARRY) {
+        n = a.cnt[p];
+        probes = a.probes[p];
+        coll = a.coll[p];
+        flag = a.flag[p];
+    }
     uint32_t c_bi = ~0u, c_lo = 0, c_hi = 0;   // the last probe's bucket (< 2^31) and its vector, until an insert
 
     uint32_t i = r0;
@@ -415,6 +427,16 @@ __global__ __launch_bounds__(kBatchBlock) void batch_replay_kernel(BatchReplayAr
     a.flag[p] = flag;
 }
 
+template <int MG>
+__global__ __launch_bounds__(kBatchBlock) void batch_replay_kernel(BatchReplayArgs a) {
+    batch_replay_lane<MG, false>(a);
+}
+
+template <int MG>
+__global__ __launch_bounds__(kBatchBlock) void batch_carried_kernel(BatchReplayArgs a) {
+    batch_replay_lane<MG, true>(a);
+}
+
 // rows [doff[p], doff[p] + cnt[p]) of the batch's MatchList = problem p's table, bucket-major
 __global__ void batch_emit_kernel(const uint64_t* __restrict__ ord, const int64_t* __restrict__ pool,
                                   const uint32_t* __restrict__ mbase, const uint32_t* __restrict__ cnt,
@@ -449,12 +471,24 @@ hipError_t launch_batch_keys(const char* ascii, const uint64_t* aoff, const uint
     return hipGetLastError();
 }
 
+// one round on the carried tables (b.ord_base set)
+static hipError_t launch_batch_carried(const BatchReplayArgs& a, dim3 grid, dim3 block, hipStream_t st) {
+    if (a.G <= 2) hipLaunchKernelGGL(batch_carried_kernel<2>, grid, block, 0, st, a);
+    else if (a.G <= 4) hipLaunchKernelGGL(batch_carried_kernel<4>, grid, block, 0, st, a);
+    else if (a.G <= 8) hipLaunchKernelGGL(batch_carried_kernel<8>, grid, block, 0, st, a);
+    else if (a.G <= 16) hipLaunchKernelGGL(batch_carried_kernel<16>, grid, block, 0, st, a);
+    else if (a.G <= 32) hipLaunchKernelGGL(batch_carried_kernel<32>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(batch_carried_kernel<64>, grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_batch_replay(const BatchReplay& b, hipStream_t st) {
     if (b.B == 0) return hipSuccess;
     BatchReplayArgs a{b.sk,  b.sv,     b.keys, b.mbase, b.nlen, b.order, b.ord, b.pool,       b.pool_cap, b.pool_n,
                       b.cnt, b.probes, b.coll, b.flag,  b.B,    b.G,     b.L,   b.kbits,      b.table_size,
-                      b.masked, b.seq_mask};
+                      b.masked, b.seq_mask, b.ord_base, b.ord_cap};
     const dim3 grid((b.B + kBatchBlock - 1) / kBatchBlock), block(kBatchBlock);
+    if (b.ord_base) return launch_batch_carried(a, grid, block, st);
     if (b.G <= 2) hipLaunchKernelGGL(batch_replay_kernel<2>, grid, block, 0, st, a);
     else if (b.G <= 4) hipLaunchKernelGGL(batch_replay_kernel<4>, grid, block, 0, st, a);
     else if (b.G <= 8) hipLaunchKernelGGL(batch_replay_kernel<8>, grid, block, 0, st, a);

@@ -164,6 +164,10 @@ struct mums_ctx {
     bool batch_result = false;
     std::vector<uint64_t> batch_off, batch_probes, batch_coll, batch_restarts;   // B + 1 / B / B / B
     mums_ctx* batch_sub = nullptr;   // problems the lanes leave out: the single-problem pipeline
+    // mums_anchor_batch / mums_anchor_tail_batch (anchor.hip): a batch result whose lists went through the tail
+    bool anchor_result = false;
+    std::vector<uint64_t> anchor_table;   // B: entries before the tail
+    DevBuf an_K, an_V, an_wlen, an_ws, an_per;
     DevBuf bt_ascii, bt_seg, bt_keys, bt_kA, bt_kB, bt_vA, bt_vB, bt_tmp, bt_ord, bt_pool, bt_per;
     bool match_log = false;  // MemHash::SetMatchLog: record the inserts (replay.hip)
     uint64_t log_n = 0;
@@ -2263,7 +2267,7 @@ int mums_ctx_destroy(mums_ctx* ctx) {
                       &ctx->side, &ctx->bst8, &ctx->cbst, &ctx->dsarr, &ctx->labx, &ctx->rkpool0, &ctx->rkpool1,
                       &ctx->rku32, &ctx->ascii_all, &ctx->keep_pool, &ctx->keep_cnt, &ctx->bt_ascii, &ctx->bt_seg,
                       &ctx->bt_keys, &ctx->bt_kA, &ctx->bt_kB, &ctx->bt_vA, &ctx->bt_vB, &ctx->bt_tmp, &ctx->bt_ord,
-                      &ctx->bt_pool, &ctx->bt_per};
+                      &ctx->bt_pool, &ctx->bt_per, &ctx->an_K, &ctx->an_V, &ctx->an_wlen, &ctx->an_ws, &ctx->an_per};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i < EV_COUNT; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
@@ -2365,6 +2369,8 @@ int mums_clear(mums_ctx* ctx) {
     ctx->batch_probes.clear();
     ctx->batch_coll.clear();
     ctx->batch_restarts.clear();
+    ctx->anchor_result = false;
+    ctx->anchor_table.clear();
     return MUMS_OK;
 }
 
@@ -3480,6 +3486,572 @@ int mums_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* probes, uint64
     if (check_ctx(ctx)) return MUMS_E_INVALID;
     if (!ctx->batch_result) return fail(ctx, MUMS_E_INVALID, "no completed mums_find_batch on this context");
     if (match_off) std::copy(ctx->batch_off.begin(), ctx->batch_off.end(), match_off);
+    if (probes) std::copy(ctx->batch_probes.begin(), ctx->batch_probes.end(), probes);
+    if (collisions) std::copy(ctx->batch_coll.begin(), ctx->batch_coll.end(), collisions);
+    if (restarts) std::copy(ctx->batch_restarts.begin(), ctx->batch_restarts.end(), restarts);
+    return MUMS_OK;
+}
+
+// ---- mums_anchor_batch / mums_anchor_tail_batch: the whole of pairwiseAnchorSearch for B problems
+// (batch.hip's rounds on a carried table, anchor.hip's tail) ----
+// rows of one list the tail's lane takes; a longer list runs its tail through the single-list
+// path on the sub-context (mums_load_matches, v2, the filter).  DESIGN.md §5l has the measurement behind 1024.
+constexpr uint64_t kAnchorTailCap = 1024;
+
+static int anchor_sub(mums_ctx* ctx, const char* who) {
+    if (ctx->batch_sub) return MUMS_OK;
+    const int rc = mums_ctx_create(ctx->device, &ctx->batch_sub);
+    if (rc != MUMS_OK) return fail(ctx, rc, std::string(who) + ": no context for the single-problem pipeline");
+    return MUMS_OK;
+}
+
+// the modes outside the batched scope, the same as mums_find_batch's
+static int anchor_refusals(mums_ctx* ctx, const std::string& who, uint32_t G) {
+    if (ctx->shard || ctx->slice) return fail(ctx, MUMS_E_UNSUPPORTED, who + " on a sharded context");
+    if (ctx->pairwise) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": PairwiseMatchFinder is not batched");
+    if (ctx->pcompat) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": the ParallelMemHash compat mode is not batched");
+    if (ctx->repeat_tol != 0 || ctx->enum_tol != 1)
+        return fail(ctx, MUMS_E_UNSUPPORTED, who + ": repeat tolerance 0 and enumeration tolerance 1 only");
+    if (have_start_points(ctx)) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": start points are not batched");
+    if (ctx->match_log) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": the match log (SetMatchLog) is not batched");
+    if (ctx->progress_on) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": the progress log (LogProgress) is not batched");
+    if (G < 2) return fail(ctx, MUMS_E_INVALID, who + ": at least two sequences per problem");
+    if (G > (uint32_t)kMaxG) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": more than 64 sequences per problem");
+    return MUMS_OK;
+}
+
+// the sub-context's list appended to len / s
+static int anchor_take_rows(mums_ctx* sub, uint32_t G, std::vector<uint64_t>& len, std::vector<int64_t>& s, uint64_t* count) {
+    uint64_t M = 0;
+    int rc = mums_result_count(sub, &M, nullptr);
+    if (!rc && M) {
+        const size_t l0 = len.size(), s0 = s.size();
+        len.resize(l0 + M);
+        s.resize(s0 + M * (size_t)G);
+        rc = mums_result_copy(sub, len.data() + l0, s.data() + s0);
+    }
+    *count = M;
+    return rc;
+}
+
+// one list's tail alone on the sub-context; its surviving rows appended to rlen / rs
+static int anchor_tail_single(mums_ctx* ctx, const char* who, uint32_t G, uint64_t n, const uint64_t* len,
+                              const int64_t* s, int eliminate_both, uint64_t min_length, std::vector<uint64_t>& rlen,
+                              std::vector<int64_t>& rs, uint64_t* count) {
+    int rc = anchor_sub(ctx, who);
+    if (rc) return rc;
+    mums_ctx* sub = ctx->batch_sub;
+    rc = mums_clear(sub);
+    if (!rc) rc = mums_load_matches(sub, G, n, len, s);
+    if (!rc) rc = mums_eliminate_overlaps_v2(sub, nullptr, 0, eliminate_both);
+    if (!rc) rc = mums_length_filter(sub, min_length);
+    if (!rc) rc = anchor_take_rows(sub, G, rlen, rs, count);
+    if (rc) return fail(ctx, rc, std::string(who) + ", single-list tail: " + sub->err);
+    (void)mums_clear(sub);
+    return MUMS_OK;
+}
+
+// problem p's whole pairwiseAnchorSearch alone on the sub-context: Clear; per round ClearSequences,
+// the round's seed, the sequences, FindMatches; EliminateOverlaps_v2; LengthFilter
+static int anchor_single(mums_ctx* ctx, uint32_t G, const char* ascii, const uint64_t* so, const uint64_t* patterns,
+                         uint32_t rounds, int eliminate_both, uint64_t min_length, std::vector<uint64_t>& rlen,
+                         std::vector<int64_t>& rs, uint64_t* count, uint64_t* table, uint64_t* probes, uint64_t* coll,
+                         uint64_t* restarts) {
+    int rc = anchor_sub(ctx, "mums_anchor_batch");
+    if (rc) return rc;
+    mums_ctx* sub = ctx->batch_sub;
+    rc = mums_clear(sub);
+    if (!rc) rc = mums_set_params(sub, 0, 1, ctx->table_size);
+    if (!rc) rc = mums_set_mask(sub, ctx->masked, ctx->seq_mask);
+    *probes = *coll = *restarts = *table = 0;
+    for (uint32_t r = 0; r < rounds && !rc; ++r) {
+        rc = mums_clear_sequences(sub);
+        if (!rc) rc = mums_set_seed(sub, patterns[r]);
+        for (uint32_t g = 0; g < G && !rc; ++g) rc = mums_add_genome(sub, ascii + so[g], so[g + 1] - so[g]);
+        if (!rc) rc = mums_find(sub);
+        if (!rc) {
+            *probes += sub->st.probes;
+            *coll = sub->st.collision_count;   // cumulative over a kept table's finds
+            *restarts += sub->st.restarts;
+        }
+    }
+    if (!rc) rc = mums_result_count(sub, table, nullptr);
+    if (!rc) rc = mums_eliminate_overlaps_v2(sub, nullptr, 0, eliminate_both);
+    if (!rc) rc = mums_length_filter(sub, min_length);
+    if (!rc) rc = anchor_take_rows(sub, G, rlen, rs, count);
+    if (rc) return fail(ctx, rc, std::string("mums_anchor_batch, single-problem pipeline: ") + sub->err);
+    (void)mums_clear(sub);
+    return MUMS_OK;
+}
+
+// The tail of every list and the context's MatchList.  List p has toff[p + 1] - toff[p] rows; fill()
+// puts them into the work arrays (d_toff, d_wlen, d_ws) on the context's stream.  routed[p]: the
+// list is final already, rcount[p] rows at rfirst[p] of rlen / rs.  A list above kAnchorTailCap
+// runs alone and joins the routed ones.  Sets ctx->batch_off and *M_out.
+using AnchorFill = std::function<hipError_t(uint64_t*, int64_t*, int64_t*)>;
+static int anchor_tail_stage(mums_ctx* ctx, const char* who, uint32_t B, uint32_t G, const std::vector<uint64_t>& toff,
+                             std::vector<uint8_t>& routed, std::vector<uint64_t>& rlen, std::vector<int64_t>& rs,
+                             std::vector<uint64_t>& rcount, std::vector<uint64_t>& rfirst, int eliminate_both,
+                             uint64_t min_length, const AnchorFill& fill, uint64_t* M_out) {
+    hipStream_t st = ctx->stream;
+    const uint64_t Tt = toff[B];
+    // toff (B + 1 u64), doff (B u64), cnt (B u32), order (B u32), skip (B bytes)
+    HIPCHK(ctx->an_per.ensure(((size_t)2 * B + 1) * 8 + (size_t)2 * B * 4 + B + 64));
+    uint64_t* d_toff = ctx->an_per.as<uint64_t>();
+    uint64_t* d_doff = d_toff + B + 1;
+    uint32_t* d_cnt = (uint32_t*)(d_doff + B);
+    uint32_t* d_order = d_cnt + B;
+    uint8_t* d_skip = (uint8_t*)(d_order + B);
+    HIPCHK(ctx->an_wlen.ensure((Tt + 1) * 8));
+    HIPCHK(ctx->an_ws.ensure((Tt + 1) * (size_t)G * 8 + 8));
+    HIPCHK(ctx->an_K.ensure((Tt + 1) * 8));
+    HIPCHK(ctx->an_V.ensure((Tt + 1) * 4 + 8));
+    HIPCHK(hipMemcpyAsync(d_toff, toff.data(), ((size_t)B + 1) * 8, hipMemcpyHostToDevice, st));
+    {
+        const hipError_t e = fill(d_toff, ctx->an_wlen.as<int64_t>(), ctx->an_ws.as<int64_t>());
+        if (e != hipSuccess) return fail(ctx, MUMS_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    std::vector<uint8_t> skip(routed);
+    std::vector<uint64_t> big_len;
+    std::vector<int64_t> big_s;
+    for (uint32_t p = 0; p < B; ++p) {
+        const uint64_t n = toff[p + 1] - toff[p];
+        if (routed[p] || n <= kAnchorTailCap) continue;
+        big_len.resize(n);
+        big_s.resize(n * (size_t)G);
+        HIPCHK(hipMemcpyAsync(big_len.data(), ctx->an_wlen.as<int64_t>() + toff[p], n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(big_s.data(), ctx->an_ws.as<int64_t>() + toff[p] * G, n * (size_t)G * 8,
+                              hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        rfirst[p] = rlen.size();
+        const int rc = anchor_tail_single(ctx, who, G, n, big_len.data(), big_s.data(), eliminate_both, min_length, rlen,
+                                          rs, &rcount[p]);
+        if (rc) return rc;
+        HIPCHK(hipSetDevice(ctx->device));
+        routed[p] = skip[p] = 1;
+    }
+    std::vector<uint32_t> order(B);
+    for (uint32_t p = 0; p < B; ++p) order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        return (skip[x] ? 0 : toff[x + 1] - toff[x]) > (skip[y] ? 0 : toff[y + 1] - toff[y]);
+    });
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_skip, skip.data(), (size_t)B, hipMemcpyHostToDevice, st));
+    AnchorTail at{};
+    at.K = ctx->an_K.as<uint64_t>();
+    at.V = ctx->an_V.as<uint32_t>();
+    at.wlen = ctx->an_wlen.as<int64_t>();
+    at.ws = ctx->an_ws.as<int64_t>();
+    at.toff = d_toff;
+    at.order = d_order;
+    at.skip = d_skip;
+    at.cnt = d_cnt;
+    at.B = B;
+    at.G = G;
+    at.eliminate_both = eliminate_both ? 1 : 0;
+    at.min_length = min_length;
+    HIPCHK(launch_anchor_tail(at, st));
+    std::vector<uint32_t> h_cnt(B, 0);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    uint64_t M = 0;
+    std::vector<uint64_t> doff(B);
+    for (uint32_t p = 0; p < B; ++p) {
+        ctx->batch_off[p] = M;
+        doff[p] = M;
+        M += routed[p] ? rcount[p] : h_cnt[p];
+    }
+    ctx->batch_off[B] = M;
+    HIPCHK(ctx->out_len.ensure((M + 1) * 8));
+    HIPCHK(ctx->out_s.ensure((M + 1) * (size_t)G * 8 + 8));
+    if (M > 0) {
+        HIPCHK(hipMemcpyAsync(d_doff, doff.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(launch_anchor_emit(at.V, at.wlen, at.ws, d_toff, d_cnt, d_doff, B, G, ctx->out_len.as<uint64_t>(),
+                                  ctx->out_s.as<int64_t>(), st));
+        for (uint32_t p = 0; p < B; ++p) {
+            if (!routed[p] || rcount[p] == 0) continue;
+            HIPCHK(hipMemcpyAsync(ctx->out_len.as<uint64_t>() + doff[p], rlen.data() + rfirst[p], rcount[p] * 8,
+                                  hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ctx->out_s.as<int64_t>() + doff[p] * G, rs.data() + rfirst[p] * G,
+                                  rcount[p] * (size_t)G * 8, hipMemcpyHostToDevice, st));
+        }
+    }
+    (void)hipEventRecord(ctx->ev[EV_OUTPUT], st);
+    HIPCHK(hipStreamSynchronize(st));
+    *M_out = M;
+    return MUMS_OK;
+}
+
+static float anchor_ms(mums_ctx* ctx, int a, int b) {
+    float f = 0;
+    return hipEventElapsedTime(&f, ctx->ev[a], ctx->ev[b]) == hipSuccess ? f : 0.0f;
+}
+
+// the context holds a finished anchor batch: one MatchList, the problems' lists in order
+static int anchor_done(mums_ctx* ctx, uint32_t G, uint64_t M, uint64_t P, uint64_t N) {
+    ctx->gt = GenomeTable{};
+    ctx->gt.G = (int)G;
+    ctx->M = M;
+    ctx->P = P;
+    ctx->N = N;
+    ctx->batch_result = true;
+    ctx->anchor_result = true;
+    ctx->list_edited = true;
+    ctx->stage_done = MUMS_STAGE_ALL;
+    return MUMS_OK;
+}
+
+int mums_anchor_tail_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const uint64_t* match_off, const uint64_t* lengths,
+                           const int64_t* starts, int eliminate_both, uint64_t min_length) {
+    if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (!have_device()) return fail(ctx, MUMS_E_NODEVICE, "no HIP device");
+    const char* who = "mums_anchor_tail_batch";
+    if (ctx->shard || ctx->slice) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_anchor_tail_batch on a sharded context");
+    if (G < 1) return fail(ctx, MUMS_E_INVALID, "mums_anchor_tail_batch: no sequences");
+    if (G > (uint32_t)kMaxG) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_anchor_tail_batch: more than 64 sequences per list");
+    if (B && !match_off) return fail(ctx, MUMS_E_INVALID, "mums_anchor_tail_batch: null list offsets");
+    for (uint32_t p = 0; p < B; ++p)
+        if (match_off[p + 1] < match_off[p]) return fail(ctx, MUMS_E_INVALID, "mums_anchor_tail_batch: list offsets decrease");
+    const uint64_t r0 = B ? match_off[0] : 0, Tt = B ? match_off[B] - r0 : 0;
+    if (Tt && (!lengths || !starts)) return fail(ctx, MUMS_E_INVALID, "mums_anchor_tail_batch: null MatchList");
+    if (Tt >= 0xFFFFFFF0ull) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_anchor_tail_batch: 2^32 rows or more in one batch (split it)");
+    int rc = mums_clear(ctx);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->batch_off.assign((size_t)B + 1, 0);
+    ctx->batch_probes.assign(B, 0);
+    ctx->batch_coll.assign(B, 0);
+    ctx->batch_restarts.assign(B, 0);
+    ctx->anchor_table.assign(B, 0);
+    if (B == 0) return anchor_done(ctx, G, 0, 0, 0);
+    hipStream_t st = ctx->stream;
+    (void)hipEventRecord(ctx->ev[EV_START], st);
+    std::vector<uint64_t> toff((size_t)B + 1);
+    for (uint32_t p = 0; p <= B; ++p) toff[p] = match_off[p] - r0;
+    for (uint32_t p = 0; p < B; ++p) ctx->anchor_table[p] = toff[p + 1] - toff[p];
+    std::vector<uint8_t> routed(B, 0);
+    std::vector<uint64_t> rlen, rcount(B, 0), rfirst(B, 0);
+    std::vector<int64_t> rs;
+    auto fill = [&](uint64_t*, int64_t* d_wlen, int64_t* d_ws) -> hipError_t {
+        hipError_t e = hipSuccess;
+        if (Tt) e = hipMemcpyAsync(d_wlen, lengths + r0, Tt * 8, hipMemcpyHostToDevice, st);
+        if (Tt && e == hipSuccess) e = hipMemcpyAsync(d_ws, starts + r0 * G, Tt * (size_t)G * 8, hipMemcpyHostToDevice, st);
+        (void)hipEventRecord(ctx->ev[EV_KEYS], st);
+        return e;
+    };
+    uint64_t M = 0;
+    rc = anchor_tail_stage(ctx, who, B, G, toff, routed, rlen, rs, rcount, rfirst, eliminate_both, min_length, fill, &M);
+    if (rc) {
+        const std::string msg = ctx->err;
+        (void)mums_clear(ctx);
+        return fail(ctx, rc, msg);
+    }
+    mums_stats& s = ctx->st;
+    s = mums_stats{};
+    s.mem_count = Tt;
+    s.ms_keys = anchor_ms(ctx, EV_START, EV_KEYS);
+    s.ms_output = anchor_ms(ctx, EV_KEYS, EV_OUTPUT);
+    s.ms_total = anchor_ms(ctx, EV_START, EV_OUTPUT);
+    return anchor_done(ctx, G, M, 0, 0);
+}
+
+int mums_anchor_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const char* ascii, const uint64_t* seq_off,
+                      const uint64_t* patterns, uint32_t rounds, int eliminate_both, uint64_t min_length) {
+    if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (!have_device()) return fail(ctx, MUMS_E_NODEVICE, "no HIP device");
+    const char* who = "mums_anchor_batch";
+    // modes outside the batched scope, before anything changes
+    int rc = anchor_refusals(ctx, who, G);
+    if (rc) return rc;
+    if (rounds < 1 || rounds > 8) return fail(ctx, MUMS_E_INVALID, "mums_anchor_batch: 1 to 8 rounds");
+    if (!patterns) return fail(ctx, MUMS_E_INVALID, "mums_anchor_batch: null seed patterns");
+    const uint64_t nseg = (uint64_t)B * G;
+    const int pbits = ceil_log2(B ? B : 1);
+    struct Round {
+        uint64_t pat;
+        int L, w, kbits;
+        SeedSpec ss;
+        uint64_t Nall = 0, N = 0;
+        std::vector<uint32_t> mbase;
+    };
+    std::vector<Round> rd(rounds);
+    bool lanes = true;
+    for (uint32_t r = 0; r < rounds; ++r) {
+        Round& x = rd[r];
+        x.pat = patterns[r];
+        if (x.pat == 0) return fail(ctx, MUMS_E_INVALID, "mums_anchor_batch: a seed pattern is 0");
+        x.L = seed_len(x.pat);
+        x.w = __builtin_popcountll(x.pat);
+        if (x.L > 32) return fail(ctx, MUMS_E_INVALID, "Mer size is too large");
+        if (x.w > 31) return fail(ctx, MUMS_E_UNSUPPORTED, "seed weight 32 not supported");
+        x.kbits = 2 * x.w + 1;
+        x.ss = make_seed_spec(x.pat, x.L, x.w);
+        lanes = lanes && x.kbits + pbits <= 64;
+    }
+    if (nseg + 1 >= (1ull << 32)) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_anchor_batch: more than 2^32 sequences");
+    if (B && !seq_off) return fail(ctx, MUMS_E_INVALID, "mums_anchor_batch: null sequence offsets");
+    for (uint64_t s = 0; s < nseg; ++s)
+        if (seq_off[s + 1] < seq_off[s]) return fail(ctx, MUMS_E_INVALID, "mums_anchor_batch: sequence offsets decrease");
+    const uint64_t a0 = B ? seq_off[0] : 0, A = B ? seq_off[nseg] - a0 : 0;
+    if (A && !ascii) return fail(ctx, MUMS_E_INVALID, "Null gnSequence pointer");
+    // the sequences' seed-mers per round; the lanes take every problem up to the cap in every round
+    const uint64_t cap = batch_problem_cap();
+    std::vector<uint8_t> routed(B, 0);
+    std::vector<uint64_t> recs((size_t)B * rounds, 0), tot(B, 0);   // recs[r * B + p]
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint64_t L = (uint64_t)rd[r].L;
+        for (uint32_t p = 0; p < B; ++p) {
+            uint64_t k = 0;
+            for (uint32_t g = 0; g < G; ++g) {
+                const uint64_t n = seq_off[(uint64_t)p * G + g + 1] - seq_off[(uint64_t)p * G + g];
+                k += n < L ? 0 : n - L + 1;
+            }
+            recs[(size_t)r * B + p] = k;
+            tot[p] += k;
+            rd[r].Nall += k;
+            if (!lanes || k > cap) routed[p] = 1;
+            if (rd[r].Nall >= 0xFFFFFFF0ull)
+                return fail(ctx, MUMS_E_UNSUPPORTED, "mums_anchor_batch: 2^32 seed-mers or more in one round of the batch (split it)");
+        }
+    }
+    // The size rule of mums_find_batch in this path's terms: the lanes' pass lasts
+    // as long as its largest problem, about kLaneUs per seed-mer of all its rounds; a problem run
+    // alone costs about kSingleUs per round plus kTailUs for its tail.  The k largest run alone.
+    std::vector<uint32_t> order(B);
+    for (uint32_t p = 0; p < B; ++p) order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        return (routed[x] ? ~0ull : tot[x]) > (routed[y] ? ~0ull : tot[y]);
+    });
+    if (lanes && !getenv("MUMS_DEV_BATCH_NO_SPLIT")) {
+        constexpr double kLaneUs = 18.0, kSingleUs = 915.0, kTailUs = 380.0;   // measured: DESIGN.md §5l
+        uint32_t k0 = 0, best = 0;
+        while (k0 < B && routed[order[k0]]) ++k0;
+        double best_cost = -1;
+        for (uint32_t k = k0; k <= B; ++k) {
+            const double cost = kLaneUs * (double)(k < B ? tot[order[k]] : 0) +
+                                (kSingleUs * (double)rounds + kTailUs) * (double)(k - k0);
+            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = k; }
+        }
+        for (uint32_t k = k0; k < best; ++k) routed[order[k]] = 1;
+    }
+    std::vector<uint64_t> aoff(nseg + 1, 0), nlen(nseg + 1, 0);
+    for (uint64_t s = 0; s < nseg; ++s) {
+        aoff[s] = seq_off[s] - a0;
+        nlen[s] = seq_off[s + 1] - seq_off[s];
+    }
+    uint64_t Nmax = 0, Nsum = 0;
+    for (uint32_t r = 0; r < rounds; ++r) {
+        Round& x = rd[r];
+        x.mbase.assign(nseg + 1, 0);
+        for (uint64_t s = 0; s < nseg; ++s) {
+            x.mbase[s] = (uint32_t)x.N;
+            if (!routed[s / G]) x.N += nlen[s] < (uint64_t)x.L ? 0 : nlen[s] - x.L + 1;
+        }
+        x.mbase[nseg] = (uint32_t)x.N;
+        Nmax = std::max(Nmax, x.N);
+        Nsum += x.N;
+    }
+    // problem p's slice of ord: an entry needs a probe and a probe two records of its round, so the
+    // table after the last round has at most the sum over the rounds of half the round's records
+    std::vector<uint32_t> obase(B, 0), ocap(B, 0);
+    uint64_t ord_words = 0;
+    for (uint32_t p = 0; p < B; ++p) {
+        uint64_t c = 0;
+        for (uint32_t r = 0; r < rounds && !routed[p]; ++r) c += recs[(size_t)r * B + p] >> 1;
+        if (ord_words + c >= 0xFFFFFFF0ull)
+            return fail(ctx, MUMS_E_UNSUPPORTED, "mums_anchor_batch: the rounds' tables need 2^32 slots or more (split the batch)");
+        obase[p] = (uint32_t)ord_words;
+        ocap[p] = (uint32_t)c;
+        ord_words += c;
+    }
+
+    // starts as MemHash::Clear does; the context's own seed pattern stays as it is
+    rc = mums_clear(ctx);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->batch_off.assign((size_t)B + 1, 0);
+    ctx->batch_probes.assign(B, 0);
+    ctx->batch_coll.assign(B, 0);
+    ctx->batch_restarts.assign(B, 0);
+    ctx->anchor_table.assign(B, 0);
+    uint64_t Nstat = 0;
+    for (const Round& x : rd) Nstat += x.Nall;
+    if (B == 0) return anchor_done(ctx, G, 0, 0, 0);
+
+    hipStream_t st = ctx->stream;
+    (void)hipEventRecord(ctx->ev[EV_START], st);
+    // per-problem device words: cnt, probes, coll, flag (B each), pool cursor, first '-' offset
+    HIPCHK(ctx->bt_per.ensure(((size_t)4 * B + 4) * 4 + 64));
+    uint32_t* d_cnt = ctx->bt_per.as<uint32_t>();
+    uint32_t *d_probes = d_cnt + B, *d_coll = d_cnt + 2 * (size_t)B, *d_flag = d_cnt + 3 * (size_t)B;
+    uint32_t* d_pool_n = d_cnt + 4 * (size_t)B;
+    unsigned long long* d_first = (unsigned long long*)(d_pool_n + 2);
+    HIPCHK(hipMemsetAsync(ctx->bt_per.p, 0, ((size_t)4 * B + 2) * 4, st));
+    HIPCHK(hipMemsetAsync(d_first, 0xFF, 8, st));
+    HIPCHK(ctx->bt_ascii.ensure(A + 64));
+    if (A) HIPCHK(hipMemcpyAsync(ctx->bt_ascii.p, ascii + a0, A, hipMemcpyHostToDevice, st));
+    // segment tables: aoff, nlen (nseg + 1 u64 each), mbase (nseg + 1 u32), order, obase, ocap (B u32 each)
+    HIPCHK(ctx->bt_seg.ensure(2 * (nseg + 1) * 8 + (nseg + 1 + 3 * (size_t)B) * 4 + 64));
+    uint64_t* d_aoff = ctx->bt_seg.as<uint64_t>();
+    uint64_t* d_nlen = d_aoff + nseg + 1;
+    uint32_t* d_mbase = (uint32_t*)(d_nlen + nseg + 1);
+    uint32_t* d_order = d_mbase + nseg + 1;
+    uint32_t *d_obase = d_order + B, *d_ocap = d_obase + B;
+    HIPCHK(hipMemcpyAsync(d_aoff, aoff.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_nlen, nlen.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_obase, obase.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_ocap, ocap.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(launch_batch_gap(ctx->bt_ascii.as<char>(), 0, A, d_first, st));
+    unsigned long long first_gap = ~0ull;
+    HIPCHK(hipMemcpyAsync(&first_gap, d_first, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (first_gap != ~0ull) {   // SortedMerList.cpp:433-437 throws for the sequence holding it
+        const uint64_t at = a0 + first_gap;
+        const uint64_t s = (uint64_t)(std::upper_bound(seq_off, seq_off + nseg + 1, at) - seq_off) - 1;
+        (void)mums_clear(ctx);
+        return fail(ctx, MUMS_E_GAP, "Gap in genome sequence: problem " + std::to_string(s / G) + " of the batch");
+    }
+
+    double ms_keys = 0, ms_sort = 0, ms_replay = 0;
+    std::vector<uint32_t> per((size_t)4 * B, 0);
+    if (Nmax > 0) {
+        const uint64_t pool_cap64 = std::min<uint64_t>(Nsum / 2 + 1, std::max<uint64_t>(Nsum / 8, 1ull << 16));
+        HIPCHK(ctx->bt_keys.ensure(Nmax * 8 + 64));
+        HIPCHK(ctx->bt_kA.ensure(Nmax * 8 + 64));
+        HIPCHK(ctx->bt_kB.ensure(Nmax * 8 + 64));
+        HIPCHK(ctx->bt_vA.ensure(Nmax * 4 + 64));
+        HIPCHK(ctx->bt_vB.ensure(Nmax * 4 + 64));
+        HIPCHK(ctx->bt_tmp.ensure(radix_tmp_bytes(Nmax) + 256));
+        HIPCHK(ctx->bt_ord.ensure((ord_words + 2) * 8));
+        HIPCHK(ctx->bt_pool.ensure(pool_cap64 * (size_t)(G + 2) * 8 + 64));
+        for (uint32_t r = 0; r < rounds; ++r) {
+            const Round& x = rd[r];
+            if (r > 0) (void)hipEventRecord(ctx->ev[EV_GROUPS], st);   // the round's start
+            if (x.N > 0) {
+                HIPCHK(hipMemcpyAsync(d_mbase, x.mbase.data(), (nseg + 1) * 4, hipMemcpyHostToDevice, st));
+                HIPCHK(launch_batch_keys(ctx->bt_ascii.as<char>(), d_aoff, d_mbase, (uint32_t)nseg, G, (uint32_t)x.N, x.ss,
+                                         x.kbits, ctx->bt_keys.as<uint64_t>(), st));
+            }
+            (void)hipEventRecord(ctx->ev[EV_KEYS], st);
+            int ob = 0;
+            if (x.N > 0)
+                HIPCHK(radix_sort<uint64_t>(ctx->bt_keys.as<uint64_t>(), nullptr, x.N, x.kbits + pbits,
+                                            ctx->bt_kA.as<uint64_t>(), ctx->bt_vA.as<uint32_t>(), ctx->bt_kB.as<uint64_t>(),
+                                            ctx->bt_vB.as<uint32_t>(), ctx->bt_tmp.p, &ob, st));
+            (void)hipEventRecord(ctx->ev[EV_SORT], st);
+            if (x.N > 0) {
+                BatchReplay br{};
+                br.sk = ob == 0 ? ctx->bt_kA.as<uint64_t>() : ctx->bt_kB.as<uint64_t>();
+                br.sv = ob == 0 ? ctx->bt_vA.as<uint32_t>() : ctx->bt_vB.as<uint32_t>();
+                br.keys = ctx->bt_keys.as<uint64_t>();
+                br.mbase = d_mbase;
+                br.nlen = d_nlen;
+                br.order = d_order;
+                br.ord = ctx->bt_ord.as<uint64_t>();
+                br.pool = ctx->bt_pool.as<int64_t>();
+                br.pool_cap = (uint32_t)pool_cap64;
+                br.pool_n = d_pool_n;
+                br.cnt = d_cnt;
+                br.probes = d_probes;
+                br.coll = d_coll;
+                br.flag = d_flag;
+                br.B = B;
+                br.G = G;
+                br.L = x.L;
+                br.kbits = x.kbits;
+                br.table_size = ctx->table_size;
+                br.masked = ctx->masked;
+                br.seq_mask = ctx->seq_mask;
+                br.ord_base = d_obase;
+                br.ord_cap = d_ocap;
+                HIPCHK(launch_batch_replay(br, st));
+            }
+            (void)hipEventRecord(ctx->ev[EV_REPLAY], st);
+            HIPCHK(hipStreamSynchronize(st));   // the next round's mbase replaces this one's; the phase times
+            ms_keys += anchor_ms(ctx, r > 0 ? EV_GROUPS : EV_START, EV_KEYS);
+            ms_sort += anchor_ms(ctx, EV_KEYS, EV_SORT);
+            ms_replay += anchor_ms(ctx, EV_SORT, EV_REPLAY);
+        }
+        HIPCHK(hipMemcpyAsync(per.data(), d_cnt, (size_t)4 * B * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    } else {
+        (void)hipEventRecord(ctx->ev[EV_REPLAY], st);
+        HIPCHK(hipStreamSynchronize(st));
+        ms_keys = anchor_ms(ctx, EV_START, EV_REPLAY);
+    }
+    const uint32_t *h_cnt = per.data(), *h_probes = h_cnt + B, *h_coll = h_cnt + 2 * (size_t)B, *h_flag = h_cnt + 3 * (size_t)B;
+
+    // the problems left out (above the cap, the size rule) or not finished in some round
+    // (MER_REPEAT_LIMIT, pool) run alone, from round 0
+    std::vector<uint64_t> rlen, rcount(B, 0), rfirst(B, 0);
+    std::vector<int64_t> rs;
+    std::vector<uint64_t> toff((size_t)B + 1, 0);
+    for (uint32_t p = 0; p < B; ++p) {
+        toff[p + 1] = toff[p];
+        if (!routed[p] && !h_flag[p]) {
+            ctx->batch_probes[p] = h_probes[p];
+            ctx->batch_coll[p] = h_coll[p];
+            ctx->anchor_table[p] = h_cnt[p];
+            toff[p + 1] += h_cnt[p];
+            continue;
+        }
+        routed[p] = 1;
+        rfirst[p] = rlen.size();
+        rc = anchor_single(ctx, G, ascii, seq_off + (uint64_t)p * G, patterns, rounds, eliminate_both, min_length, rlen,
+                           rs, &rcount[p], &ctx->anchor_table[p], &ctx->batch_probes[p], &ctx->batch_coll[p],
+                           &ctx->batch_restarts[p]);
+        if (rc) {
+            const std::string msg = ctx->err;
+            (void)mums_clear(ctx);
+            return fail(ctx, rc, msg);
+        }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    auto fill = [&](uint64_t* d_toff, int64_t* d_wlen, int64_t* d_ws) -> hipError_t {
+        if (toff[B] == 0) return hipSuccess;
+        return launch_anchor_gather(ctx->bt_ord.as<uint64_t>(), d_obase, ctx->bt_pool.as<int64_t>(), d_toff, B, G, d_wlen,
+                                    d_ws, st);
+    };
+    uint64_t M = 0;
+    rc = anchor_tail_stage(ctx, who, B, G, toff, routed, rlen, rs, rcount, rfirst, eliminate_both, min_length, fill, &M);
+    if (rc) {
+        const std::string msg = ctx->err;
+        (void)mums_clear(ctx);
+        return fail(ctx, rc, msg);
+    }
+    uint64_t P = 0, C = 0, R = 0, E = 0;
+    for (uint32_t p = 0; p < B; ++p) {
+        P += ctx->batch_probes[p];
+        C += ctx->batch_coll[p];
+        R += ctx->batch_restarts[p];
+        E += ctx->anchor_table[p];
+    }
+    mums_stats& s = ctx->st;
+    s = mums_stats{};
+    s.seedmers = Nstat;
+    s.probes = P;
+    s.mem_count = E;
+    s.collision_count = C;
+    s.restarts = R;
+    s.repeat_limit_groups = R;
+    s.key_bytes = 8;
+    for (const Round& x : rd) s.sort_passes += (uint64_t)((x.kbits + pbits + 7) / 8);
+    s.ms_keys = ms_keys;
+    s.ms_sort = ms_sort;
+    s.ms_replay = ms_replay;
+    s.ms_output = anchor_ms(ctx, EV_REPLAY, EV_OUTPUT);
+    s.ms_total = anchor_ms(ctx, EV_START, EV_OUTPUT);
+    return anchor_done(ctx, G, M, P, Nstat);
+}
+
+int mums_anchor_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* table_entries, uint64_t* probes,
+                           uint64_t* collisions, uint64_t* restarts) {
+    if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (!ctx->batch_result || !ctx->anchor_result)
+        return fail(ctx, MUMS_E_INVALID, "no completed mums_anchor_batch / mums_anchor_tail_batch on this context");
+    if (match_off) std::copy(ctx->batch_off.begin(), ctx->batch_off.end(), match_off);
+    if (table_entries) std::copy(ctx->anchor_table.begin(), ctx->anchor_table.end(), table_entries);
     if (probes) std::copy(ctx->batch_probes.begin(), ctx->batch_probes.end(), probes);
     if (collisions) std::copy(ctx->batch_coll.begin(), ctx->batch_coll.end(), collisions);
     if (restarts) std::copy(ctx->batch_restarts.begin(), ctx->batch_restarts.end(), restarts);

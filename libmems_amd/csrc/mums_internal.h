@@ -730,14 +730,47 @@ struct BatchReplay {
     uint32_t table_size;
     int masked;
     uint64_t seq_mask;
+    // a table carried over rounds (mums_anchor_batch); null: one round, problem p's
+    // slice of ord at mbase[p * G] / 2 with half its records as capacity
+    const uint32_t* ord_base = nullptr;   // B: first word of problem p's slice of ord
+    const uint32_t* ord_cap = nullptr;    // B: its capacity
 };
 // flag[p] != 0: the problem was not finished (1: a masked-key group above MER_REPEAT_LIMIT, 2: the
 // entry pool is full, 4: internal) and has no entries; the caller runs it alone
+// With ord_base set the lane goes on from the round before: cnt[p] entries already in its slice,
+// probes / coll added to, a flag kept (a flagged problem does nothing more); cnt, probes, coll and
+// flag are zeroed by the caller before round 0 only.  Stored entries compare with mer = 0, probes
+// with this round's L, and ExtendMatch reads this round's keys.
 hipError_t launch_batch_replay(const BatchReplay& b, hipStream_t st);
 // problem p's entries -> rows [doff[p], doff[p] + cnt[p]) of the MatchList
 hipError_t launch_batch_emit(const uint64_t* ord, const int64_t* pool, const uint32_t* mbase, const uint32_t* cnt,
                              const uint64_t* doff, uint32_t B, uint32_t G, uint64_t* out_len, int64_t* out_s,
                              hipStream_t st);
+
+// anchor.hip: pairwiseAnchorSearch's tail (EliminateOverlaps_v2 over every sequence, then
+// LengthFilter) for B lists in one pass.  List p = rows [toff[p], toff[p + 1]) of wlen / ws
+// (lengths, G starts per row; cropped in place).
+// problem p's table (ord slice at obase[p], entries in pool: batch.hip) -> its rows of wlen / ws
+hipError_t launch_anchor_gather(const uint64_t* ord, const uint32_t* obase, const int64_t* pool, const uint64_t* toff,
+                                uint32_t B, uint32_t G, int64_t* wlen, int64_t* ws, hipStream_t st);
+struct AnchorTail {
+    uint64_t* K;              // toff[B] words of scratch: sort keys
+    uint32_t* V;              // toff[B] words: out, list p's surviving row ids (list-local) at V[toff[p] ..]
+    int64_t* wlen;
+    int64_t* ws;
+    const uint64_t* toff;     // B + 1
+    const uint32_t* order;    // lane -> problem (lists of similar size share a wave)
+    const uint8_t* skip;      // B: 1 = not run here (cnt[p] = 0)
+    uint32_t* cnt;            // B: surviving rows
+    uint32_t B, G;
+    int eliminate_both;
+    uint64_t min_length;
+};
+hipError_t launch_anchor_tail(const AnchorTail& a, hipStream_t st);
+// list p's surviving rows -> rows [doff[p], doff[p] + cnt[p]) of the MatchList
+hipError_t launch_anchor_emit(const uint32_t* V, const int64_t* wlen, const int64_t* ws, const uint64_t* toff,
+                              const uint32_t* cnt, const uint64_t* doff, uint32_t B, uint32_t G, uint64_t* out_len,
+                              int64_t* out_s, hipStream_t st);
 
 // smlsort.hip: the std::sort order of equal seed mers in every SortedMerList
 // (MemorySML.cpp:54) for flagged runs.  Slot space = genome-major SML slots (= global

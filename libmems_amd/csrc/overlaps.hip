@@ -22,12 +22,13 @@
 #include <algorithm>
 #include <vector>
 
+#include "anchor_lane.h"
 #include "mums_internal.h"
 
 namespace mums {
 namespace {
 
-constexpr uint32_t kDel = 0xFFFFFFFFu;
+constexpr uint32_t kDel = lane::kDeleted;
 constexpr uint32_t kLeaf = 16;   // _S_threshold
 
 struct SortSeg {
@@ -309,21 +310,9 @@ __global__ void cluster_bound_kernel(const uint32_t* __restrict__ cstart, uint32
     if (k >= 2) atomicAdd(cap, (unsigned long long)(k * (k - 1) / 2));
 }
 
-__device__ __forceinline__ int mult_of(const int64_t* s, int G) {
-    int m = 0;
-    for (int g = 0; g < G; ++g) m += s[g] != 0;
-    return m;
-}
-__device__ __forceinline__ void crop_start(int64_t* len, int64_t* s, int G, int64_t a) {   // UngappedLocalAlignment.h:138
-    *len -= a;
-    for (int g = 0; g < G; ++g)
-        if (s[g] > 0) s[g] += a;
-}
-__device__ __forceinline__ void crop_end(int64_t* len, int64_t* s, int G, int64_t a) {     // :147
-    *len -= a;
-    for (int g = 0; g < G; ++g)
-        if (s[g] < 0) s[g] -= a;
-}
+using lane::crop_end;
+using lane::crop_start;
+using lane::mult_of;
 
 // the reference's matchI / nextI loops (Aligner.cpp:81-160) over one cluster
 __global__ void cluster_sim_kernel(uint32_t* V, int64_t* plen, int64_t* ps, int G, int seqI,
@@ -395,29 +384,8 @@ __global__ void cluster_sim_kernel(uint32_t* V, int64_t* plen, int64_t* ps, int 
     if (keeps) atomicAdd(nkeep, keeps);
 }
 
-// checkConsistent (ProgressiveAligner.h:272-291): the same b->Start - a->Start in every
-// sequence where both are defined, and more than one such sequence
-__device__ __forceinline__ bool check_consistent(const int64_t* a, const int64_t* b, int G) {
-    bool consistent = true, have = false;
-    int64_t o = 0;
-    int inter = 0;
-    for (int g = 0; g < G; ++g) {
-        if (a[g] == 0 || b[g] == 0) continue;
-        ++inter;
-        if (!have) {
-            o = b[g] - a[g];
-            have = true;
-        }
-        if (o != b[g] - a[g]) consistent = false;
-    }
-    return consistent && inter > 1;
-}
-
-// EliminateOverlaps_v2's matchI / nextI loops (ProgressiveAligner.h:319-382) over one cluster.
-// Length(seqI) (UngappedLocalAlignment.h:48-55) is m_length here: every match of a cluster is
-// defined in seqI.  CropRight / CropLeft(diff, seqI) (:169-184) take the orientation of seqI.
-// processNewMatch (:260-271) sets Start(seqI) to NO_MATCH and then asks for Length(seqI) > 0,
-// which is 0 for a Match: the cut-off copy is never kept, so none is made here.
+// EliminateOverlaps_v2's matchI / nextI loops (ProgressiveAligner.h:319-382) over one cluster: the
+// walk of anchor_lane.h, which anchor.hip runs over a whole small list per lane
 __global__ void cluster_sim_v2_kernel(uint32_t* V, int64_t* plen, int64_t* ps, int G, int seqI,
                                       const uint32_t* __restrict__ cstart, uint32_t C, int eliminate_both,
                                       unsigned long long* __restrict__ ndel) {
@@ -425,47 +393,7 @@ __global__ void cluster_sim_v2_kernel(uint32_t* V, int64_t* plen, int64_t* ps, i
     if (c >= C) return;
     const int64_t a = cstart[c], b = cstart[c + 1];
     if (b - a < 2) return;
-    unsigned long long dels = 0;
-    for (int64_t mi = a; mi < b; mi++) {
-        if (V[mi] == kDel) continue;
-        for (int64_t nj = mi + 1; nj < b; nj++) {
-            if (V[nj] == kDel) continue;
-            bool deleted_i = false;
-            const uint64_t I = V[mi], J = V[nj];
-            int64_t* sI = ps + I * G;
-            int64_t* sJ = ps + J * G;
-            const int64_t startI = sI[seqI], lenI = plen[I], startJ = sJ[seqI];
-            int64_t diff = (startJ < 0 ? -startJ : startJ) - (startI < 0 ? -startI : startI) - lenI;
-            if (diff >= 0) break;   // there are no more overlaps
-            diff = -diff;
-            // both decided before any crop of the pair
-            const int mJ = mult_of(sJ, G), mI = mult_of(sI, G);
-            const bool i_smaller = mJ > mI || (mJ == mI && plen[J] > lenI);
-            const bool both = eliminate_both && !check_consistent(sI, sJ, G);
-            if (both || i_smaller) {   // :345
-                if (diff >= lenI) {
-                    V[mi] = kDel;
-                    deleted_i = true;
-                    ++dels;
-                } else if (startI > 0) {
-                    crop_end(&plen[I], sI, G, diff);     // CropRight, forward
-                } else {
-                    crop_start(&plen[I], sI, G, diff);   // CropRight, reverse
-                }
-            }
-            if (both || !i_smaller) {   // :363 (runs on nextI also after matchI was deleted)
-                if (diff >= plen[J]) {
-                    V[nj] = kDel;
-                    ++dels;
-                } else if (startJ > 0) {
-                    crop_start(&plen[J], sJ, G, diff);   // CropLeft, forward
-                } else {
-                    crop_end(&plen[J], sJ, G, diff);     // CropLeft, reverse
-                }
-            }
-            if (deleted_i) break;
-        }
-    }
+    const unsigned long long dels = lane::v2_walk(V, plen, ps, G, seqI, a, b, eliminate_both);
     if (dels) atomicAdd(ndel, dels);
 }
 

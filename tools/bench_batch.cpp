@@ -2,7 +2,8 @@
 //
 // Through the C ABI only (no interpreter in either number), the library loaded at run time so
 // that one binary times a build without mums_find_batch too:
-//   bench_batch --lib PATH [--workload w1|w2] [--reps 5] [--mode loop|batch|both] [--oracle PATH]
+//   bench_batch --lib PATH [--workload w1|w2] [--reps 5] [--mode loop|batch|both|anchor-loop|anchor-batch|anchor]
+//               [--oracle PATH]
 // Workloads (fixed generator seed, default seed per problem as pairwiseAnchorSearch chooses it,
 // ProgressiveAligner.cpp:615-616, table size 40000), measured from host ASCII to host MatchList:
 //   w1  4096 problems, two sequences, lengths uniform in [200, 4000], the partner a copy with 5 %
@@ -10,6 +11,12 @@
 //   w2  256 problems of 2 x 50000 bases, the same otherwise
 // loop  = mums_clear / mums_add_genome x2 / mums_find / mums_result_copy per problem on one context
 // batch = problems grouped by seed pattern, one mums_find_batch + mums_result_copy per pattern
+// The anchor modes time the whole of pairwiseAnchorSearch with seed families (ranks 0-2 of each
+// problem's default weight, eliminate_both 0, min_length 12):
+// anchor-loop  = per problem mums_clear; per rank mums_clear_sequences / mums_set_seed / mums_add_genome x2 /
+//                mums_find; mums_eliminate_overlaps_v2(NULL, 0, 0); mums_length_filter(12); mums_result_copy
+// anchor-batch = problems grouped by weight, one mums_anchor_batch + mums_result_copy per weight
+// anchor       = both, and the lists compared row by row
 // --oracle: the CPU oracle (oracle/build/libmums_oracle.so) on one thread, timed once, and every
 // list compared with it.
 // Prints one JSON object per line: the repetitions' milliseconds, their median and spread
@@ -47,7 +54,15 @@ struct Api {
     decltype(&mums_default_seed_weight) default_seed_weight;
     decltype(&mums_find_batch) find_batch;   // null in a build without it
     decltype(&mums_batch_info) batch_info;
+    decltype(&mums_clear_sequences) clear_sequences;
+    decltype(&mums_eliminate_overlaps_v2) eliminate_overlaps_v2;
+    decltype(&mums_length_filter) length_filter;
+    decltype(&mums_anchor_batch) anchor_batch;   // null in a build without it
+    decltype(&mums_anchor_batch_info) anchor_batch_info;
 };
+
+constexpr int kFamilyRanks = 3;          // --seed-family: ranks 0, 1, 2 (ProgressiveAligner.cpp:619-653)
+constexpr uint64_t kAnchorMinLength = 12;   // MIN_ANCHOR_LENGTH + 3 (:659)
 
 template <typename F>
 bool sym(void* h, const char* name, F* f, bool required = true) {
@@ -70,6 +85,7 @@ struct Workload {
     std::string ascii;               // all sequences, problem-major
     std::vector<uint64_t> off;       // 2 B + 1
     std::vector<uint64_t> pattern;   // per problem (0: default weight 0, no search)
+    std::vector<uint32_t> weight;    // per problem: its default seed weight
     uint32_t B = 0;
 };
 
@@ -96,6 +112,7 @@ Workload make_workload(const Api& a, const std::string& name) {
         w.off.push_back(w.ascii.size());
         const uint32_t wt = a.default_seed_weight((s0.size() + s1.size()) / 2);
         w.pattern.push_back(wt ? (uint64_t)a.get_seed((int)wt, 0) : 0);
+        w.weight.push_back(wt);
     }
     return w;
 }
@@ -198,6 +215,89 @@ bool run_batch(const Api& a, mums_ctx* ctx, const Workload& w, Lists* out, mums_
     return true;
 }
 
+bool take_list(const Api& a, mums_ctx* ctx, Lists* out) {
+    uint64_t M = 0;
+    CK(a.result_count(ctx, &M, nullptr));
+    const size_t l0 = out->len.size();
+    out->len.resize(l0 + M);
+    out->st.resize((l0 + M) * 2);
+    if (M) CK(a.result_copy(ctx, out->len.data() + l0, out->st.data() + l0 * 2));
+    return true;
+}
+
+bool run_anchor_loop(const Api& a, mums_ctx* ctx, const Workload& w, Lists* out) {
+    out->moff.assign(1, 0);
+    out->len.clear();
+    out->st.clear();
+    for (uint32_t p = 0; p < w.B; ++p) {
+        if (w.weight[p]) {
+            CK(a.clear(ctx));
+            for (int r = 0; r < kFamilyRanks; ++r) {
+                CK(a.clear_sequences(ctx));
+                CK(a.set_seed(ctx, (uint64_t)a.get_seed((int)w.weight[p], r)));
+                for (int g = 0; g < 2; ++g)
+                    CK(a.add_genome(ctx, w.ascii.data() + w.off[2 * p + g], w.off[2 * p + g + 1] - w.off[2 * p + g]));
+                CK(a.find(ctx));
+            }
+            CK(a.eliminate_overlaps_v2(ctx, nullptr, 0, 0));
+            CK(a.length_filter(ctx, kAnchorMinLength));
+            if (!take_list(a, ctx, out)) return false;
+        }
+        out->moff.push_back(out->len.size());
+    }
+    return true;
+}
+
+bool run_anchor_batch(const Api& a, mums_ctx* ctx, const Workload& w, Lists* out, mums_stats* phases) {
+    std::map<uint32_t, std::vector<uint32_t>> groups;
+    for (uint32_t p = 0; p < w.B; ++p)
+        if (w.weight[p]) groups[w.weight[p]].push_back(p);
+    std::vector<std::vector<uint64_t>> plen(w.B);
+    std::vector<std::vector<int64_t>> pst(w.B);
+    *phases = mums_stats{};
+    for (const auto& kv : groups) {
+        const std::vector<uint32_t>& idx = kv.second;
+        std::string blob;
+        std::vector<uint64_t> off(1, 0);
+        for (uint32_t p : idx)
+            for (int g = 0; g < 2; ++g) {
+                blob.append(w.ascii, w.off[2 * p + g], w.off[2 * p + g + 1] - w.off[2 * p + g]);
+                off.push_back(blob.size());
+            }
+        uint64_t pats[kFamilyRanks];
+        for (int r = 0; r < kFamilyRanks; ++r) pats[r] = (uint64_t)a.get_seed((int)kv.first, r);
+        CK(a.anchor_batch(ctx, (uint32_t)idx.size(), 2, blob.data(), off.data(), pats, kFamilyRanks, 0, kAnchorMinLength));
+        uint64_t M = 0;
+        CK(a.result_count(ctx, &M, nullptr));
+        std::vector<uint64_t> len(M), mo(idx.size() + 1);
+        std::vector<int64_t> st(M * 2);
+        if (M) CK(a.result_copy(ctx, len.data(), st.data()));
+        CK(a.anchor_batch_info(ctx, mo.data(), nullptr, nullptr, nullptr, nullptr));
+        for (size_t j = 0; j < idx.size(); ++j) {
+            plen[idx[j]].assign(len.begin() + mo[j], len.begin() + mo[j + 1]);
+            pst[idx[j]].assign(st.begin() + 2 * mo[j], st.begin() + 2 * mo[j + 1]);
+        }
+        mums_stats s;
+        CK(a.get_stats(ctx, &s));
+        phases->ms_keys += s.ms_keys;
+        phases->ms_sort += s.ms_sort;
+        phases->ms_replay += s.ms_replay;
+        phases->ms_output += s.ms_output;
+        phases->ms_total += s.ms_total;
+        phases->restarts += s.restarts;
+        phases->mem_count += s.mem_count;
+    }
+    out->moff.assign(1, 0);
+    out->len.clear();
+    out->st.clear();
+    for (uint32_t p = 0; p < w.B; ++p) {
+        out->len.insert(out->len.end(), plen[p].begin(), plen[p].end());
+        out->st.insert(out->st.end(), pst[p].begin(), pst[p].end());
+        out->moff.push_back(out->len.size());
+    }
+    return true;
+}
+
 void report(const char* what, const std::string& wl, const std::string& lib, std::vector<double> ms, uint64_t hash,
             uint64_t matches, const char* extra) {
     std::vector<double> s = ms;
@@ -222,7 +322,7 @@ int main(int argc, char** argv) {
         else if (k == "--reps" && i + 1 < argc) reps = atoi(argv[++i]);
         else if (k == "--mode" && i + 1 < argc) mode = argv[++i];
         else if (k == "--oracle" && i + 1 < argc) oracle = argv[++i];
-        else { fprintf(stderr, "usage: bench_batch --lib PATH [--workload w1|w2] [--reps N] [--mode loop|batch|both] [--oracle PATH]\n"); return 2; }
+        else { fprintf(stderr, "usage: bench_batch --lib PATH [--workload w1|w2] [--reps N] [--mode loop|batch|both|anchor-loop|anchor-batch|anchor] [--oracle PATH]\n"); return 2; }
     }
     if (lib.empty() || (wl != "w1" && wl != "w2") || reps < 1) { fprintf(stderr, "bench_batch: --lib PATH and --workload w1|w2 required\n"); return 2; }
     void* h = dlopen(lib.c_str(), RTLD_NOW | RTLD_LOCAL);
@@ -237,6 +337,63 @@ int main(int argc, char** argv) {
     sym(h, "mums_find_batch", &a.find_batch, false);
     sym(h, "mums_batch_info", &a.batch_info, false);
     if (!ok) return 2;
+    sym(h, "mums_clear_sequences", &a.clear_sequences, false);
+    sym(h, "mums_eliminate_overlaps_v2", &a.eliminate_overlaps_v2, false);
+    sym(h, "mums_length_filter", &a.length_filter, false);
+    sym(h, "mums_anchor_batch", &a.anchor_batch, false);
+    sym(h, "mums_anchor_batch_info", &a.anchor_batch_info, false);
+    if (mode.rfind("anchor", 0) == 0) {
+        const bool a_loop = mode != "anchor-batch", a_batch = mode != "anchor-loop";
+        if (a_loop && !(a.clear_sequences && a.eliminate_overlaps_v2 && a.length_filter)) {
+            fprintf(stderr, "bench_batch: the library lacks mums_clear_sequences / mums_eliminate_overlaps_v2\n");
+            return 2;
+        }
+        if (a_batch && !(a.anchor_batch && a.anchor_batch_info)) {
+            fprintf(stderr, "bench_batch: the library has no mums_anchor_batch\n");
+            return 2;
+        }
+        const Workload w = make_workload(a, wl);
+        mums_ctx* ctx = nullptr;
+        if (a.ctx_create(0, &ctx) != MUMS_OK) { fprintf(stderr, "bench_batch: no HIP device\n"); return 3; }
+        a.set_params(ctx, 0, 1, 40000);
+        Lists loop, batch;
+        if (a_loop) {
+            std::vector<double> ms;
+            if (!run_anchor_loop(a, ctx, w, &loop)) return 1;   // warm-up: buffers, code objects
+            for (int r = 0; r < reps; ++r) {
+                const double t0 = now_ms();
+                if (!run_anchor_loop(a, ctx, w, &loop)) return 1;
+                ms.push_back(now_ms() - t0);
+            }
+            report("anchor_loop", wl, lib, ms, loop.hash(), loop.len.size(), "");
+        }
+        if (a_batch) {
+            std::vector<double> ms;
+            mums_stats last{};
+            if (!run_anchor_batch(a, ctx, w, &batch, &last)) return 1;
+            for (int r = 0; r < reps; ++r) {
+                const double t0 = now_ms();
+                if (!run_anchor_batch(a, ctx, w, &batch, &last)) return 1;
+                ms.push_back(now_ms() - t0);
+            }
+            char extra[320];
+            snprintf(extra, sizeof extra,
+                     ", \"phase_ms\": {\"upload_keys\": %.3f, \"sort\": %.3f, \"replay\": %.3f, \"single_tail_emit\": %.3f, "
+                     "\"pass_total\": %.3f}, \"restarts\": %llu, \"table_entries\": %llu",
+                     last.ms_keys, last.ms_sort, last.ms_replay, last.ms_output, last.ms_total,
+                     (unsigned long long)last.restarts, (unsigned long long)last.mem_count);
+            report("anchor_batch", wl, lib, ms, batch.hash(), batch.len.size(), extra);
+        }
+        int status = 0;
+        if (a_loop && a_batch) {
+            const bool eq = loop == batch;
+            printf("{\"what\": \"compare\", \"workload\": \"%s\", \"anchor_batch_equals_loop\": %s}\n", wl.c_str(),
+                   eq ? "true" : "false");
+            if (!eq) status = 1;
+        }
+        a.ctx_destroy(ctx);
+        return status;
+    }
     const bool want_loop = mode != "batch", want_batch = mode != "loop";
     if (want_batch && !a.find_batch) {
         if (mode == "batch") { fprintf(stderr, "bench_batch: the library has no mums_find_batch\n"); return 2; }

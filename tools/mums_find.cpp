@@ -13,6 +13,12 @@
 //       Appendix-C generator seeded per problem): "# problem k" + its MatchList text, first from
 //       MemHash::FindMatchesBatch (default seeds), then after "== loop" from a loop of
 //       Clear + FindMatches with the same seeds on the same object
+//   mums_find anchor B n p | anchor files a0 b0 a1 b1 ...   B gap problems as in `batch`, or one per pair of
+//       files: "# problem k" + its anchor list,
+//       first from MemHash::AnchorSearchBatch (seed families, default weights), then after "== loop"
+//       from the loop of pairwiseAnchorSearch (Clear; per rank ClearSequences + FindMatches;
+//       EliminateOverlaps_v2; LengthFilter(12)) on the same object, then after "== tail" from
+//       AnchorTailBatch over the problems' family tables
 //   mums_find smldump G n weight p g stride  genome g's deferred SML read back: every entry
 //       (position, mer) through operator[], then FindMer of every stride-th entry's mer
 #include <unistd.h>
@@ -175,6 +181,61 @@ int main(int argc, char** argv) {
             }
             std::cout << os.str();
             std::cerr << "problems " << B << " probes " << probes << "\n";
+        } catch (const std::exception& e) {
+            std::cerr << "error: " << e.what() << "\n";
+            return 1;
+        }
+        return 0;
+    }
+    if (mode == "anchor" && argc >= 5) {
+        const bool files = std::string(argv[2]) == "files";   // anchor files a0 b0 a1 b1 ...: one problem per pair
+        const int B = files ? (argc - 3) / 2 : atoi(argv[2]);
+        const uint64_t n = files ? 0 : strtoull(argv[3], nullptr, 10);
+        const double p = files ? 0 : atof(argv[4]);
+        try {
+            std::vector<std::vector<std::string>> problems;
+            for (int k = 0; k < B; ++k) {
+                if (files) problems.push_back({read_seq(argv[3 + 2 * k]), read_seq(argv[4 + 2 * k])});
+                else problems.push_back(generate(2, n / (uint64_t)(k + 1), p, 12345 + (uint64_t)k));
+            }
+            mums::MemHash mh(0);
+            std::vector<mums::MatchList> lists, tables((size_t)B), tails;
+            mh.AnchorSearchBatch(problems, lists);
+            std::ostringstream os;
+            uint64_t entries = 0;
+            for (uint64_t v : mh.AnchorBatchInfo().table_entries) entries += v;
+            for (int k = 0; k < B; ++k) {
+                os << "# problem " << k << '\n';
+                for (const auto& m : lists[k]) os << m << '\n';
+            }
+            os << "== loop\n";
+            for (int k = 0; k < B; ++k) {
+                os << "# problem " << k << '\n';
+                const uint32_t w = mums_default_seed_weight((problems[k][0].size() + problems[k][1].size()) / 2);
+                if (!w) continue;
+                mh.Clear();
+                mums::MatchList ml;
+                for (int seed_rank = 0; seed_rank < 3; ++seed_rank) {
+                    mh.ClearSequences();
+                    mh.SetSeed((uint64_t)mums_get_seed((int)w, seed_rank));
+                    ml.clear();
+                    ml.seq_table = problems[k];
+                    mh.FindMatches(ml);
+                }
+                mh.GetMatchList(tables[(size_t)k]);
+                mh.EliminateOverlaps_v2(false);
+                mh.LengthFilter(12);
+                mh.GetMatchList(ml);
+                for (const auto& m : ml) os << m << '\n';
+            }
+            os << "== tail\n";
+            mh.AnchorTailBatch(tables, 2, tails);
+            for (int k = 0; k < B; ++k) {
+                os << "# problem " << k << '\n';
+                for (const auto& m : tails[k]) os << m << '\n';
+            }
+            std::cout << os.str();
+            std::cerr << "problems " << B << " table entries " << entries << "\n";
         } catch (const std::exception& e) {
             std::cerr << "error: " << e.what() << "\n";
             return 1;
