@@ -10,6 +10,7 @@
 // is shown in INTEGRATION.md.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <memory>
 #include <ostream>
@@ -286,55 +287,19 @@ public:
     // sequences and table, and it leaves the seed of the last group set.
     virtual void FindMatchesBatch(const std::vector<std::vector<std::string>>& problems, std::vector<MatchList>& out,
                                   const std::vector<uint64_t>& seeds = {}) {
-        const size_t B = problems.size();
-        if (!seeds.empty() && seeds.size() != B) throw InvalidData("FindMatchesBatch: one seed pattern per problem");
-        const size_t G = B ? problems[0].size() : 2;
-        out.assign(B, MatchList());
-        batch_ = BatchCounters();
-        batch_.probes.assign(B, 0);
-        batch_.collisions.assign(B, 0);
-        batch_.restarts.assign(B, 0);
-        std::vector<uint64_t> pats;      // distinct patterns in order of first appearance
+        const size_t G = problems.empty() ? 2 : problems[0].size();
+        batch_begin(problems.size(), out, false);
+        std::vector<uint64_t> pats;
         std::vector<std::vector<size_t>> members;
-        for (size_t p = 0; p < B; ++p) {
-            if (problems[p].size() != G) throw InvalidData("FindMatchesBatch: every problem needs the same sequence count");
-            uint64_t pat = 0;
-            if (!seeds.empty()) {
-                pat = seeds[p];
-            } else {
-                uint64_t total = 0;
-                for (const std::string& s : problems[p]) total += s.size();
-                const uint32_t w = mums_default_seed_weight(G ? total / G : 0);
-                pat = w ? (uint64_t)mums_get_seed((int)w, 0) : 0;
-            }
-            if (pat == 0) continue;
-            size_t k = 0;
-            while (k < pats.size() && pats[k] != pat) ++k;
-            if (k == pats.size()) { pats.push_back(pat); members.emplace_back(); }
-            members[k].push_back(p);
-        }
-        if (pats.empty()) check(mums_clear(ctx_));
+        batch_groups("FindMatchesBatch", "pattern", problems, seeds, pats, members,
+                     [](uint32_t w) { return w ? (uint64_t)mums_get_seed((int)w, 0) : 0; });
         for (size_t k = 0; k < pats.size(); ++k) {
-            const std::vector<size_t>& idx = members[k];
             std::string blob;
-            std::vector<uint64_t> off(1, 0);
-            for (size_t p : idx)
-                for (const std::string& s : problems[p]) {
-                    blob += s;
-                    off.push_back(blob.size());
-                }
+            std::vector<uint64_t> off;
+            batch_blob(problems, members[k], blob, off);
             check(mums_set_seed(ctx_, pats[k]));
-            check(mums_find_batch(ctx_, (uint32_t)idx.size(), (uint32_t)G, blob.data(), off.data()));
-            MatchList all;
-            GetMatchList(all);
-            std::vector<uint64_t> mo(idx.size() + 1), pr(idx.size()), co(idx.size()), rs(idx.size());
-            check(mums_batch_info(ctx_, mo.data(), pr.data(), co.data(), rs.data()));
-            for (size_t j = 0; j < idx.size(); ++j) {
-                out[idx[j]].assign(all.begin() + mo[j], all.begin() + mo[j + 1]);
-                batch_.probes[idx[j]] = pr[j];
-                batch_.collisions[idx[j]] = co[j];
-                batch_.restarts[idx[j]] = rs[j];
-            }
+            check(mums_find_batch(ctx_, (uint32_t)members[k].size(), (uint32_t)G, blob.data(), off.data()));
+            batch_collect(members[k], out, false);
         }
     }
     const BatchCounters& BatchInfo() const { return batch_; }
@@ -353,48 +318,20 @@ public:
     virtual void AnchorSearchBatch(const std::vector<std::vector<std::string>>& problems, std::vector<MatchList>& out,
                                    bool seed_families = true, const std::vector<uint32_t>& weights = {},
                                    bool eliminate_both = false, uint64_t min_length = 12) {
-        const size_t B = problems.size();
-        if (!weights.empty() && weights.size() != B) throw InvalidData("AnchorSearchBatch: one seed weight per problem");
-        const size_t G = B ? problems[0].size() : 2;
-        out.assign(B, MatchList());
-        anchor_ = AnchorCounters();
-        anchor_.table_entries.assign(B, 0);
-        anchor_.probes.assign(B, 0);
-        anchor_.collisions.assign(B, 0);
-        anchor_.restarts.assign(B, 0);
-        std::vector<uint32_t> ws;        // distinct weights in order of first appearance
+        const size_t G = problems.empty() ? 2 : problems[0].size();
+        batch_begin(problems.size(), out, true);
+        std::vector<uint32_t> ws;
         std::vector<std::vector<size_t>> members;
-        for (size_t p = 0; p < B; ++p) {
-            if (problems[p].size() != G) throw InvalidData("AnchorSearchBatch: every problem needs the same sequence count");
-            uint32_t w = 0;
-            if (!weights.empty()) {
-                w = weights[p];
-            } else {
-                uint64_t total = 0;
-                for (const std::string& s : problems[p]) total += s.size();
-                w = mums_default_seed_weight(G ? total / G : 0);
-            }
-            if (w == 0) continue;
-            size_t k = 0;
-            while (k < ws.size() && ws[k] != w) ++k;
-            if (k == ws.size()) { ws.push_back(w); members.emplace_back(); }
-            members[k].push_back(p);
-        }
-        if (ws.empty()) check(mums_clear(ctx_));
+        batch_groups("AnchorSearchBatch", "weight", problems, weights, ws, members, [](uint32_t w) { return w; });
         for (size_t k = 0; k < ws.size(); ++k) {
-            const std::vector<size_t>& idx = members[k];
             std::string blob;
-            std::vector<uint64_t> off(1, 0);
-            for (size_t p : idx)
-                for (const std::string& s : problems[p]) {
-                    blob += s;
-                    off.push_back(blob.size());
-                }
+            std::vector<uint64_t> off;
+            batch_blob(problems, members[k], blob, off);
             std::vector<uint64_t> pats;
             for (int r = 0; r < (seed_families ? 3 : 1); ++r) pats.push_back((uint64_t)mums_get_seed((int)ws[k], r));
-            check(mums_anchor_batch(ctx_, (uint32_t)idx.size(), (uint32_t)G, blob.data(), off.data(), pats.data(),
+            check(mums_anchor_batch(ctx_, (uint32_t)members[k].size(), (uint32_t)G, blob.data(), off.data(), pats.data(),
                                     (uint32_t)pats.size(), eliminate_both ? 1 : 0, min_length));
-            anchor_collect(idx, out);
+            batch_collect(members[k], out, true);
         }
     }
     // pairwiseAnchorSearch's tail on the caller's lists in one device pass (mums_anchor_tail_batch):
@@ -415,15 +352,10 @@ public:
         }
         check(mums_anchor_tail_batch(ctx_, (uint32_t)B, seq_count, off.data(), len.data(), st.data(), eliminate_both ? 1 : 0,
                                      min_length));
-        out.assign(B, MatchList());
-        anchor_ = AnchorCounters();
-        anchor_.table_entries.assign(B, 0);
-        anchor_.probes.assign(B, 0);
-        anchor_.collisions.assign(B, 0);
-        anchor_.restarts.assign(B, 0);
+        batch_begin(B, out, true);
         std::vector<size_t> idx(B);
         for (size_t p = 0; p < B; ++p) idx[p] = p;
-        anchor_collect(idx, out);
+        batch_collect(idx, out, true);
     }
     const AnchorCounters& AnchorBatchInfo() const { return anchor_; }
     // MemHash::CreateMatches (MemHash.cpp:104-107)
@@ -615,18 +547,68 @@ protected:
     uint32_t repeat_tol_ = 0, enum_tol_ = 1, table_size_ = 40000;
     BatchCounters batch_;
     AnchorCounters anchor_;
-    // the context's anchor batch result -> the lists and counters of the problems idx
-    void anchor_collect(const std::vector<size_t>& idx, std::vector<MatchList>& out) {
+    // the per-problem counters of a find batch or an anchor batch, in the order of the C calls
+    std::array<std::vector<uint64_t>*, 4> batch_counters(bool anchor) {
+        if (anchor) return {&anchor_.table_entries, &anchor_.probes, &anchor_.collisions, &anchor_.restarts};
+        return {nullptr, &batch_.probes, &batch_.collisions, &batch_.restarts};
+    }
+    // the result of a batched call before its first group: empty lists, counters of 0
+    void batch_begin(size_t B, std::vector<MatchList>& out, bool anchor) {
+        out.assign(B, MatchList());
+        for (std::vector<uint64_t>* v : batch_counters(anchor))
+            if (v) v->assign(B, 0);
+    }
+    // The problems grouped by their key, a seed pattern or weight: given[p], else key_of(the default
+    // weight of the mean length).  keys in order of first appearance; key 0: no search; no key at
+    // all: the call is a Clear()
+    template <typename Key, typename F>
+    void batch_groups(const std::string& who, const char* what, const std::vector<std::vector<std::string>>& problems,
+                      const std::vector<Key>& given, std::vector<Key>& keys, std::vector<std::vector<size_t>>& members,
+                      F key_of) {
+        const size_t B = problems.size(), G = B ? problems[0].size() : 2;
+        if (!given.empty() && given.size() != B) throw InvalidData(who + ": one seed " + what + " per problem");
+        for (size_t p = 0; p < B; ++p) {
+            if (problems[p].size() != G) throw InvalidData(who + ": every problem needs the same sequence count");
+            Key key = 0;
+            if (!given.empty()) {
+                key = given[p];
+            } else {
+                uint64_t total = 0;
+                for (const std::string& s : problems[p]) total += s.size();
+                key = (Key)key_of(mums_default_seed_weight(G ? total / G : 0));
+            }
+            if (key == 0) continue;
+            size_t k = 0;
+            while (k < keys.size() && keys[k] != key) ++k;
+            if (k == keys.size()) { keys.push_back(key); members.emplace_back(); }
+            members[k].push_back(p);
+        }
+        if (keys.empty()) check(mums_clear(ctx_));
+    }
+    // the sequences of the problems idx as the batched calls take them
+    static void batch_blob(const std::vector<std::vector<std::string>>& problems, const std::vector<size_t>& idx,
+                           std::string& blob, std::vector<uint64_t>& off) {
+        off.assign(1, 0);
+        for (size_t p : idx)
+            for (const std::string& s : problems[p]) {
+                blob += s;
+                off.push_back(blob.size());
+            }
+    }
+    // the context's batch result -> the lists and counters of the problems idx
+    void batch_collect(const std::vector<size_t>& idx, std::vector<MatchList>& out, bool anchor) {
         MatchList all;
         GetMatchList(all);
-        std::vector<uint64_t> mo(idx.size() + 1), te(idx.size()), pr(idx.size()), co(idx.size()), rs(idx.size());
-        check(mums_anchor_batch_info(ctx_, mo.data(), te.data(), pr.data(), co.data(), rs.data()));
-        for (size_t j = 0; j < idx.size(); ++j) {
+        const size_t n = idx.size();
+        std::vector<uint64_t> mo(n + 1), col[4] = {std::vector<uint64_t>(n), std::vector<uint64_t>(n),
+                                                   std::vector<uint64_t>(n), std::vector<uint64_t>(n)};
+        check(anchor ? mums_anchor_batch_info(ctx_, mo.data(), col[0].data(), col[1].data(), col[2].data(), col[3].data())
+                     : mums_batch_info(ctx_, mo.data(), col[1].data(), col[2].data(), col[3].data()));
+        const std::array<std::vector<uint64_t>*, 4> dst = batch_counters(anchor);
+        for (size_t j = 0; j < n; ++j) {
             out[idx[j]].assign(all.begin() + mo[j], all.begin() + mo[j + 1]);
-            anchor_.table_entries[idx[j]] = te[j];
-            anchor_.probes[idx[j]] = pr[j];
-            anchor_.collisions[idx[j]] = co[j];
-            anchor_.restarts[idx[j]] = rs[j];
+            for (int c = 0; c < 4; ++c)
+                if (dst[c]) (*dst[c])[idx[j]] = col[c][j];
         }
     }
 };

@@ -319,6 +319,19 @@ def anchor_seed_groups(problems: Sequence[Sequence[bytes]], seed_families: bool 
     return ws, groups, patterns
 
 
+# the per-problem counters of BatchInfo() / AnchorBatchInfo(), after "matches" in the order of the C calls
+_BATCH_KEYS = ("matches", "probes", "collisions", "restarts")
+_ANCHOR_KEYS = ("matches", "table_entries", "probes", "collisions", "restarts")
+
+
+def _batch_blob(problems, idx):
+    """The sequences of the problems idx as the batched calls take them: (ascii, seq_off)."""
+    seqs = [s for p in idx for s in problems[p]]
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+    return b"".join(seqs), off
+
+
 @dataclass
 class MatchList:
     """GetMatchList output (MemHash.h:182-203): lengths[M], starts[M, G] (1-based, signed, 0 = NO_MATCH)."""
@@ -474,36 +487,14 @@ class MemHash:
         are grouped by pattern, one mums_find_batch per pattern.  Like Clear() + FindMatches, the
         call drops the object's sequences and table; afterwards the object holds the last
         group's list and seed pattern, and BatchInfo() every problem's counters."""
-        problems = [tuple(s.encode() if isinstance(s, str) else bytes(s) for s in prob) for prob in problems]
-        B = len(problems)
-        G = len(problems[0]) if B else 2
-        if any(len(prob) != G for prob in problems):
-            raise ValueError("FindMatchesBatch: every problem needs the same number of sequences")
+        problems, G, out, info = self._batch_begin("FindMatchesBatch", problems, _BATCH_KEYS)
         patterns, groups = batch_seed_groups(problems, seeds)
-        out: List[Optional[MatchList]] = [None] * B
-        info = {k: np.zeros(B, dtype=np.uint64) for k in ("matches", "probes", "collisions", "restarts")}
-        self._keepalive.clear()
-        for p in range(B):
-            if patterns[p] == 0:
-                out[p] = MatchList(np.zeros(0, dtype=np.uint64), np.zeros((0, G), dtype=np.int64))
-        if not groups:
-            self._check(self._lib.mums_clear(self._ctx))
+        self._batch_skip([p for p, pat in enumerate(patterns) if pat == 0], G, out, groups)
         for pat, idx in groups.items():
-            blob = b"".join(s for p in idx for s in problems[p])
-            off = np.zeros(len(idx) * G + 1, dtype=np.uint64)
-            off[1:] = np.cumsum([len(s) for p in idx for s in problems[p]], dtype=np.uint64)
+            blob, off = _batch_blob(problems, idx)
             self.SetSeed(pat)
             self._check(self._lib.mums_find_batch(self._ctx, len(idx), G, blob, off.ctypes.data))
-            ml = self.GetMatchList()
-            mo = np.zeros(len(idx) + 1, dtype=np.uint64)
-            pr, co, rs = (np.zeros(len(idx), dtype=np.uint64) for _ in range(3))
-            self._check(self._lib.mums_batch_info(self._ctx, mo.ctypes.data, pr.ctypes.data, co.ctypes.data,
-                                                  rs.ctypes.data))
-            for k, p in enumerate(idx):
-                a, b = int(mo[k]), int(mo[k + 1])
-                out[p] = MatchList(ml.lengths[a:b].copy(), ml.starts[a:b].copy())
-                info["matches"][p] = b - a
-                info["probes"][p], info["collisions"][p], info["restarts"][p] = pr[k], co[k], rs[k]
+            self._batch_collect(idx, G, out, info)
         self._batch_info = info
         return out  # type: ignore[return-value]
 
@@ -514,19 +505,39 @@ class MemHash:
             raise MumsError(MUMS_E_INVALID, "no FindMatchesBatch on this object")
         return self._batch_info
 
-    def _anchor_collect(self, idx, G, out, info) -> None:
-        """The context's anchor batch result -> the lists and counters of the problems idx."""
+    def _batch_begin(self, who, problems, keys):
+        """The start of a batched call: (problems as tuples of bytes, G, the result lists, the counters)."""
+        problems = [tuple(s.encode() if isinstance(s, str) else bytes(s) for s in prob) for prob in problems]
+        B = len(problems)
+        G = len(problems[0]) if B else 2
+        if any(len(prob) != G for prob in problems):
+            raise ValueError(f"{who}: every problem needs the same number of sequences")
+        self._keepalive.clear()
+        return problems, G, [None] * B, {k: np.zeros(B, dtype=np.uint64) for k in keys}
+
+    def _batch_skip(self, skipped, G, out, groups) -> None:
+        """Empty lists for the problems without a search; a call without any search is a Clear()."""
+        for p in skipped:
+            out[p] = MatchList(np.zeros(0, dtype=np.uint64), np.zeros((0, G), dtype=np.int64))
+        if not groups:
+            self._check(self._lib.mums_clear(self._ctx))
+
+    def _batch_collect(self, idx, G, out, info) -> None:
+        """The context's batch result -> the lists and counters of the problems idx; info's keys
+        say whether it is a find batch's or an anchor batch's."""
         ml = self.GetMatchList()
-        n = len(idx)
-        mo = np.zeros(n + 1, dtype=np.uint64)
-        te, pr, co, rs = (np.zeros(n, dtype=np.uint64) for _ in range(4))
-        self._check(self._lib.mums_anchor_batch_info(self._ctx, mo.ctypes.data, te.ctypes.data, pr.ctypes.data,
-                                                     co.ctypes.data, rs.ctypes.data))
+        mo = np.zeros(len(idx) + 1, dtype=np.uint64)
+        cols = {k: np.zeros(len(idx), dtype=np.uint64) for k in info if k != "matches"}
+        call = self._lib.mums_anchor_batch_info if "table_entries" in info else self._lib.mums_batch_info
+        self._check(call(self._ctx, mo.ctypes.data, *[c.ctypes.data for c in cols.values()]))
         for k, p in enumerate(idx):
             a, b = int(mo[k]), int(mo[k + 1])
             out[p] = MatchList(ml.lengths[a:b].copy(), ml.starts[a:b].copy().reshape(b - a, G))
             info["matches"][p] = b - a
-            info["table_entries"][p], info["probes"][p], info["collisions"][p], info["restarts"][p] = te[k], pr[k], co[k], rs[k]
+            for key, col in cols.items():
+                info[key][p] = col[k]
+
+    _anchor_collect = _batch_collect   # the name the anchor tests' direct mums_anchor_batch calls collect through
 
     def AnchorSearchBatch(self, problems: Sequence[Sequence[bytes]], seed_families: bool = True, weights=None,
                           eliminate_both: bool = False, min_length: int = 12) -> List[MatchList]:
@@ -539,28 +550,15 @@ class MemHash:
         an empty list and no device work (:626-633).  Returns one MatchList per problem with starts
         in the problem's own sequences (the translation of :661-670 is the caller's);
         AnchorBatchInfo() has every problem's counters.  The object's own seed is not changed."""
-        problems = [tuple(s.encode() if isinstance(s, str) else bytes(s) for s in prob) for prob in problems]
-        B = len(problems)
-        G = len(problems[0]) if B else 2
-        if any(len(prob) != G for prob in problems):
-            raise ValueError("AnchorSearchBatch: every problem needs the same number of sequences")
+        problems, G, out, info = self._batch_begin("AnchorSearchBatch", problems, _ANCHOR_KEYS)
         ws, groups, patterns = anchor_seed_groups(problems, seed_families, weights)
-        out: List[Optional[MatchList]] = [None] * B
-        info = {k: np.zeros(B, dtype=np.uint64) for k in ("matches", "table_entries", "probes", "collisions", "restarts")}
-        self._keepalive.clear()
-        for p in range(B):
-            if ws[p] == 0:
-                out[p] = MatchList(np.zeros(0, dtype=np.uint64), np.zeros((0, G), dtype=np.int64))
-        if not groups:
-            self._check(self._lib.mums_clear(self._ctx))
+        self._batch_skip([p for p, w in enumerate(ws) if w == 0], G, out, groups)
         for w, idx in groups.items():
-            blob = b"".join(s for p in idx for s in problems[p])
-            off = np.zeros(len(idx) * G + 1, dtype=np.uint64)
-            off[1:] = np.cumsum([len(s) for p in idx for s in problems[p]], dtype=np.uint64)
+            blob, off = _batch_blob(problems, idx)
             pats = np.asarray(patterns[w], dtype=np.uint64)
             self._check(self._lib.mums_anchor_batch(self._ctx, len(idx), G, blob, off.ctypes.data, pats.ctypes.data,
                                                     len(pats), int(bool(eliminate_both)), int(min_length)))
-            self._anchor_collect(idx, G, out, info)
+            self._batch_collect(idx, G, out, info)
         self._anchor_info = info
         return out  # type: ignore[return-value]
 
@@ -583,8 +581,8 @@ class MemHash:
         self._check(self._lib.mums_anchor_tail_batch(self._ctx, B, G, off.ctypes.data, lengths.ctypes.data,
                                                      starts.ctypes.data, int(bool(eliminate_both)), int(min_length)))
         out: List[Optional[MatchList]] = [None] * B
-        info = {k: np.zeros(B, dtype=np.uint64) for k in ("matches", "table_entries", "probes", "collisions", "restarts")}
-        self._anchor_collect(list(range(B)), G, out, info)
+        info = {k: np.zeros(B, dtype=np.uint64) for k in _ANCHOR_KEYS}
+        self._batch_collect(list(range(B)), G, out, info)
         self._anchor_info = info
         return out  # type: ignore[return-value]
 

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/mums.h"
+#include "batch_plan.h"
 #include "match_device.h"
 #include "mums_internal.h"
 #include "seed_device.h"
@@ -2158,10 +2159,13 @@ int shard_msd_bits(int w) {
     return std::min(kMaxMsdBits, std::max(kbits - 32, std::min(8, kbits - 1)));
 }
 
-int ceil_log2(uint64_t x) {
-    int b = 0;
-    while ((1ull << b) < x) ++b;
-    return b;
+using batch::ceil_log2;
+
+// the per-problem vectors of a batch result (B + 1 / B each), or none
+void batch_vectors(mums_ctx* ctx, size_t B, bool hold) {
+    ctx->batch_off.assign(hold ? B + 1 : 0, 0);
+    for (auto* v : {&ctx->batch_probes, &ctx->batch_coll, &ctx->batch_restarts, &ctx->anchor_table})
+        v->assign(hold ? B : 0, 0);
 }
 
 // sharded mode: global table from the layout, local table (owned genomes, global bases)
@@ -2364,13 +2368,8 @@ int mums_clear(mums_ctx* ctx) {
     ctx->keep_on = ctx->table_fresh = ctx->list_edited = false;
     ctx->keep_n = ctx->keep_coll = ctx->carry_coll = 0;
     ctx->pool_c = 0;
-    ctx->batch_result = false;
-    ctx->batch_off.clear();
-    ctx->batch_probes.clear();
-    ctx->batch_coll.clear();
-    ctx->batch_restarts.clear();
-    ctx->anchor_result = false;
-    ctx->anchor_table.clear();
+    ctx->batch_result = ctx->anchor_result = false;
+    batch_vectors(ctx, 0, false);
     return MUMS_OK;
 }
 
@@ -3178,7 +3177,10 @@ int mums_load_matches(mums_ctx* ctx, uint32_t seq_count, uint64_t count, const u
     return MUMS_OK;
 }
 
-// ---- mums_find_batch: B independent FindMatches in one pass (batch.hip) ----
+// ---- The batched finds.  mums_find_batch: B independent FindMatches in one
+// pass (batch.hip).  mums_anchor_batch / mums_anchor_tail_batch: the whole of pairwiseAnchorSearch
+// for B problems (batch.hip's rounds on a carried table, anchor.hip's tail).  One host engine:
+// check, plan (batch_plan.h), device setup, rounds, fallbacks, tail or emit, stats ----
 // seed-mers of one problem the lanes take; a larger problem runs through the single-problem
 // pipeline, whose tiles it fills (MUMS_DEV_BATCH_CAP: development A/B)
 static uint64_t batch_problem_cap() {
@@ -3186,327 +3188,68 @@ static uint64_t batch_problem_cap() {
     return e ? strtoull(e, nullptr, 10) : 200000ull;
 }
 
-// problem p alone on the sub-context: its list appended to len / s, its counters
-static int batch_single(mums_ctx* ctx, uint32_t G, const char* ascii, const uint64_t* so, std::vector<uint64_t>& len,
-                        std::vector<int64_t>& s, uint64_t* count, uint64_t* probes, uint64_t* coll, uint64_t* restarts) {
-    if (!ctx->batch_sub) {
-        const int rc = mums_ctx_create(ctx->device, &ctx->batch_sub);
-        if (rc != MUMS_OK) return fail(ctx, rc, "mums_find_batch: no context for the single-problem pipeline");
-    }
-    mums_ctx* sub = ctx->batch_sub;
-    int rc = mums_clear(sub);
-    if (!rc) rc = mums_set_seed(sub, ctx->seed);
-    if (!rc) rc = mums_set_params(sub, 0, 1, ctx->table_size);
-    if (!rc) rc = mums_set_mask(sub, ctx->masked, ctx->seq_mask);
-    for (uint32_t g = 0; g < G && !rc; ++g) rc = mums_add_genome(sub, ascii + so[g], so[g + 1] - so[g]);
-    if (!rc) rc = mums_find(sub);
-    uint64_t M = 0;
-    if (!rc) rc = mums_result_count(sub, &M, nullptr);
-    if (!rc && M) {
-        const size_t l0 = len.size(), s0 = s.size();
-        len.resize(l0 + M);
-        s.resize(s0 + M * (size_t)G);
-        rc = mums_result_copy(sub, len.data() + l0, s.data() + s0);
-    }
-    if (rc) return fail(ctx, rc, std::string("mums_find_batch, single-problem pipeline: ") + sub->err);
-    *count = M;
-    *probes = sub->st.probes;
-    *coll = sub->st.collision_count;
-    *restarts = sub->st.restarts;
-    (void)mums_clear(sub);
-    return MUMS_OK;
-}
-
-int mums_find_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const char* ascii, const uint64_t* seq_off) {
-    if (check_ctx(ctx)) return MUMS_E_INVALID;
-    if (!have_device()) return fail(ctx, MUMS_E_NODEVICE, "no HIP device");
-    // modes outside the batched scope, before anything changes
-    if (ctx->shard || ctx->slice) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch on a sharded context");
-    if (ctx->pairwise) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: PairwiseMatchFinder is not batched");
-    if (ctx->pcompat) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: the ParallelMemHash compat mode is not batched");
-    if (ctx->repeat_tol != 0 || ctx->enum_tol != 1)
-        return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: repeat tolerance 0 and enumeration tolerance 1 only");
-    if (have_start_points(ctx)) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: start points are not batched");
-    if (ctx->match_log) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: the match log (SetMatchLog) is not batched");
-    if (ctx->progress_on) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: the progress log (LogProgress) is not batched");
-    if (G < 2) return fail(ctx, MUMS_E_INVALID, "mums_find_batch: at least two sequences per problem");
-    if (G > (uint32_t)kMaxG) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: more than 64 sequences per problem");
-    if (ctx->seed == 0) return fail(ctx, MUMS_E_INVALID, "mums_find_batch: the seed pattern must be set (mums_set_seed)");
-    const uint64_t nseg = (uint64_t)B * G;
-    if (nseg + 1 >= (1ull << 32)) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: more than 2^32 sequences");
-    if (B && !seq_off) return fail(ctx, MUMS_E_INVALID, "mums_find_batch: null sequence offsets");
-    for (uint64_t s = 0; s < nseg; ++s)
-        if (seq_off[s + 1] < seq_off[s]) return fail(ctx, MUMS_E_INVALID, "mums_find_batch: sequence offsets decrease");
-    const uint64_t a0 = B ? seq_off[0] : 0, A = B ? seq_off[nseg] - a0 : 0;
-    if (A && !ascii) return fail(ctx, MUMS_E_INVALID, "Null gnSequence pointer");
-    const uint64_t pat = ctx->seed;
-    const int L = seed_len(pat), w = __builtin_popcountll(pat);
-    if (L > 32) return fail(ctx, MUMS_E_INVALID, "Mer size is too large");
-    if (w > 31) return fail(ctx, MUMS_E_UNSUPPORTED, "seed weight 32 not supported");
-    // the sequences' seed-mers; the lanes' pass takes every problem up to the cap
-    const int kbits = 2 * w + 1, pbits = ceil_log2(B ? B : 1);
-    const bool lanes = kbits + pbits <= 64;
-    const uint64_t cap = batch_problem_cap();
-    std::vector<uint32_t> mbase(nseg + 1, 0);
-    std::vector<uint64_t> aoff(nseg + 1, 0), nlen(nseg + 1, 0);
-    std::vector<uint8_t> routed(B, 0);
-    std::vector<uint64_t> recs(B, 0);
-    uint64_t Nall = 0, N = 0;
-    for (uint32_t p = 0; p < B; ++p) {
-        uint64_t r = 0;
-        for (uint32_t g = 0; g < G; ++g) {
-            const uint64_t n = seq_off[(uint64_t)p * G + g + 1] - seq_off[(uint64_t)p * G + g];
-            r += n < (uint64_t)L ? 0 : n - L + 1;
-        }
-        recs[p] = r;
-        Nall += r;
-        routed[p] = (!lanes || r > cap) ? 1 : 0;
-        if (Nall >= 0xFFFFFFF0ull)
-            return fail(ctx, MUMS_E_UNSUPPORTED, "mums_find_batch: 2^32 seed-mers or more in one batch (split it)");
-    }
-    // The lanes run side by side, so their pass lasts as long as its largest problem (about
-    // kLaneUs per seed-mer), while a problem run alone costs about kSingleUs whatever its size:
-    // the k largest problems run alone, k minimising the sum of the two
-    std::vector<uint32_t> order(B);
-    for (uint32_t p = 0; p < B; ++p) order[p] = p;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-        return (routed[x] ? ~0ull : recs[x]) > (routed[y] ? ~0ull : recs[y]);
-    });
-    if (lanes && !getenv("MUMS_DEV_BATCH_NO_SPLIT")) {
-        constexpr double kLaneUs = 10.0, kSingleUs = 1000.0;
-        uint32_t k0 = 0, best = 0;
-        while (k0 < B && routed[order[k0]]) ++k0;
-        double best_cost = -1;
-        for (uint32_t k = k0; k <= B; ++k) {
-            const double cost = kLaneUs * (double)(k < B ? recs[order[k]] : 0) + kSingleUs * (double)(k - k0);
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = k; }
-        }
-        for (uint32_t k = k0; k < best; ++k) routed[order[k]] = 1;
-    }
-    for (uint64_t s = 0; s < nseg; ++s) {
-        const uint64_t n = seq_off[s + 1] - seq_off[s];
-        aoff[s] = seq_off[s] - a0;
-        nlen[s] = n;
-        mbase[s] = (uint32_t)N;
-        if (!routed[s / G]) N += n < (uint64_t)L ? 0 : n - L + 1;
-    }
-    mbase[nseg] = (uint32_t)N;
-
-    // starts as MemHash::Clear does
-    int rc = mums_clear(ctx);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->pattern = pat;
-    ctx->L = L;
-    ctx->w = w;
-    ctx->ss = make_seed_spec(pat, L, w);
-    ctx->gt = GenomeTable{};
-    ctx->gt.G = (int)G;
-    ctx->batch_off.assign((size_t)B + 1, 0);
-    ctx->batch_probes.assign(B, 0);
-    ctx->batch_coll.assign(B, 0);
-    ctx->batch_restarts.assign(B, 0);
-    auto done = [&](uint64_t M, uint64_t P) {
-        ctx->M = M;
-        ctx->P = P;
-        ctx->N = Nall;
-        ctx->batch_result = true;
-        ctx->list_edited = true;
-        ctx->stage_done = MUMS_STAGE_ALL;
-        return MUMS_OK;
-    };
-    if (B == 0) return done(0, 0);
-
-    hipStream_t st = ctx->stream;
-    (void)hipEventRecord(ctx->ev[EV_START], st);
-    // per-problem device words: cnt, probes, coll, flag (B each), pool cursor, first '-' offset
-    const size_t per_words = (size_t)4 * B + 4;
-    HIPCHK(ctx->bt_per.ensure(per_words * 4 + 64));
-    uint32_t* d_cnt = ctx->bt_per.as<uint32_t>();
-    uint32_t *d_probes = d_cnt + B, *d_coll = d_cnt + 2 * (size_t)B, *d_flag = d_cnt + 3 * (size_t)B;
-    uint32_t* d_pool_n = d_cnt + 4 * (size_t)B;
-    unsigned long long* d_first = (unsigned long long*)(d_pool_n + 2);
-    HIPCHK(hipMemsetAsync(ctx->bt_per.p, 0, ((size_t)4 * B + 2) * 4, st));
-    HIPCHK(hipMemsetAsync(d_first, 0xFF, 8, st));
-    HIPCHK(ctx->bt_ascii.ensure(A + 64));
-    if (A) HIPCHK(hipMemcpyAsync(ctx->bt_ascii.p, ascii + a0, A, hipMemcpyHostToDevice, st));
-    // segment tables: aoff (nseg + 1 u64), nlen (nseg + 1 u64), doff (B u64), mbase (nseg + 1 u32), order (B u32)
-    const size_t seg_bytes = (2 * (nseg + 1) + B) * 8 + (nseg + 1 + B) * 4;
-    HIPCHK(ctx->bt_seg.ensure(seg_bytes + 64));
-    uint64_t* d_aoff = ctx->bt_seg.as<uint64_t>();
-    uint64_t *d_nlen = d_aoff + nseg + 1, *d_doff = d_nlen + nseg + 1;
-    uint32_t* d_mbase = (uint32_t*)(d_doff + B);
-    uint32_t* d_order = d_mbase + nseg + 1;
-    // (order: problems of similar size share a wave; the ones run alone come first and have no seed-mers here)
-    HIPCHK(hipMemcpyAsync(d_aoff, aoff.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_nlen, nlen.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_mbase, mbase.data(), (nseg + 1) * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_order, order.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(launch_batch_gap(ctx->bt_ascii.as<char>(), 0, A, d_first, st));
-    unsigned long long first_gap = ~0ull;
-    HIPCHK(hipMemcpyAsync(&first_gap, d_first, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (first_gap != ~0ull) {   // SortedMerList.cpp:433-437 throws for the sequence holding it
-        const uint64_t at = a0 + first_gap;
-        const uint64_t s = (uint64_t)(std::upper_bound(seq_off, seq_off + nseg + 1, at) - seq_off) - 1;
-        ctx->batch_off.clear();
-        ctx->batch_probes.clear();
-        ctx->batch_coll.clear();
-        ctx->batch_restarts.clear();
-        return fail(ctx, MUMS_E_GAP, "Gap in genome sequence: problem " + std::to_string(s / G) + " of the batch");
-    }
-
-    std::vector<uint32_t> per((size_t)4 * B, 0);
-    if (N > 0) {
-        const uint64_t pool_cap64 = std::min<uint64_t>(N / 2 + 1, std::max<uint64_t>(N / 8, 1ull << 16));
-        HIPCHK(ctx->bt_keys.ensure(N * 8 + 64));
-        HIPCHK(ctx->bt_kA.ensure(N * 8 + 64));
-        HIPCHK(ctx->bt_kB.ensure(N * 8 + 64));
-        HIPCHK(ctx->bt_vA.ensure(N * 4 + 64));
-        HIPCHK(ctx->bt_vB.ensure(N * 4 + 64));
-        HIPCHK(ctx->bt_tmp.ensure(radix_tmp_bytes(N) + 256));
-        HIPCHK(ctx->bt_ord.ensure((N / 2 + 2) * 8));
-        HIPCHK(ctx->bt_pool.ensure(pool_cap64 * (size_t)(G + 2) * 8 + 64));
-        HIPCHK(launch_batch_keys(ctx->bt_ascii.as<char>(), d_aoff, d_mbase, (uint32_t)nseg, G, (uint32_t)N, ctx->ss, kbits,
-                                 ctx->bt_keys.as<uint64_t>(), st));
-        (void)hipEventRecord(ctx->ev[EV_KEYS], st);
-        int ob = 0;
-        HIPCHK(radix_sort<uint64_t>(ctx->bt_keys.as<uint64_t>(), nullptr, N, kbits + pbits, ctx->bt_kA.as<uint64_t>(),
-                                    ctx->bt_vA.as<uint32_t>(), ctx->bt_kB.as<uint64_t>(), ctx->bt_vB.as<uint32_t>(),
-                                    ctx->bt_tmp.p, &ob, st));
-        (void)hipEventRecord(ctx->ev[EV_SORT], st);
-        BatchReplay br{};
-        br.sk = ob == 0 ? ctx->bt_kA.as<uint64_t>() : ctx->bt_kB.as<uint64_t>();
-        br.sv = ob == 0 ? ctx->bt_vA.as<uint32_t>() : ctx->bt_vB.as<uint32_t>();
-        br.keys = ctx->bt_keys.as<uint64_t>();
-        br.mbase = d_mbase;
-        br.nlen = d_nlen;
-        br.order = d_order;
-        br.ord = ctx->bt_ord.as<uint64_t>();
-        br.pool = ctx->bt_pool.as<int64_t>();
-        br.pool_cap = (uint32_t)pool_cap64;
-        br.pool_n = d_pool_n;
-        br.cnt = d_cnt;
-        br.probes = d_probes;
-        br.coll = d_coll;
-        br.flag = d_flag;
-        br.B = B;
-        br.G = G;
-        br.L = L;
-        br.kbits = kbits;
-        br.table_size = ctx->table_size;
-        br.masked = ctx->masked;
-        br.seq_mask = ctx->seq_mask;
-        HIPCHK(launch_batch_replay(br, st));
-        (void)hipEventRecord(ctx->ev[EV_REPLAY], st);
-        HIPCHK(hipMemcpyAsync(per.data(), d_cnt, (size_t)4 * B * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    } else {
-        (void)hipEventRecord(ctx->ev[EV_KEYS], st);
-        (void)hipEventRecord(ctx->ev[EV_SORT], st);
-        (void)hipEventRecord(ctx->ev[EV_REPLAY], st);
-    }
-    const uint32_t *h_cnt = per.data(), *h_probes = h_cnt + B, *h_coll = h_cnt + 2 * (size_t)B, *h_flag = h_cnt + 3 * (size_t)B;
-
-    // the problems left out (above the cap) or not finished (MER_REPEAT_LIMIT, pool) run alone
-    std::vector<uint64_t> rlen;
-    std::vector<int64_t> rs;
-    std::vector<uint64_t> rcount(B, 0), rfirst(B, 0);
-    uint64_t nrouted = 0;
-    for (uint32_t p = 0; p < B; ++p) {
-        if (!routed[p] && !h_flag[p]) {
-            ctx->batch_probes[p] = h_probes[p];
-            ctx->batch_coll[p] = h_coll[p];
-            continue;
-        }
-        routed[p] = 1;
-        ++nrouted;
-        rfirst[p] = rlen.size();
-        rc = batch_single(ctx, G, ascii, seq_off + (uint64_t)p * G, rlen, rs, &rcount[p], &ctx->batch_probes[p],
-                          &ctx->batch_coll[p], &ctx->batch_restarts[p]);
-        if (rc) {
-            const std::string msg = ctx->err;
-            (void)mums_clear(ctx);
-            return fail(ctx, rc, msg);
-        }
-    }
-    HIPCHK(hipSetDevice(ctx->device));
-    uint64_t M = 0, P = 0, C = 0, R = 0;
-    std::vector<uint64_t> doff(B);
-    for (uint32_t p = 0; p < B; ++p) {
-        ctx->batch_off[p] = M;
-        doff[p] = M;
-        M += routed[p] ? rcount[p] : h_cnt[p];
-        P += ctx->batch_probes[p];
-        C += ctx->batch_coll[p];
-        R += ctx->batch_restarts[p];
-    }
-    ctx->batch_off[B] = M;
-    HIPCHK(ctx->out_len.ensure((M + 1) * 8));
-    HIPCHK(ctx->out_s.ensure((M + 1) * (size_t)G * 8 + 8));
-    if (M > 0) {
-        if (N > 0) {
-            HIPCHK(hipMemcpyAsync(d_doff, doff.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(launch_batch_emit(ctx->bt_ord.as<uint64_t>(), ctx->bt_pool.as<int64_t>(), d_mbase, d_cnt, d_doff, B, G,
-                                     ctx->out_len.as<uint64_t>(), ctx->out_s.as<int64_t>(), st));
-        }
-        for (uint32_t p = 0; p < B && nrouted; ++p) {
-            if (!routed[p] || rcount[p] == 0) continue;
-            HIPCHK(hipMemcpyAsync(ctx->out_len.as<uint64_t>() + doff[p], rlen.data() + rfirst[p], rcount[p] * 8,
-                                  hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(ctx->out_s.as<int64_t>() + doff[p] * G, rs.data() + rfirst[p] * G,
-                                  rcount[p] * (size_t)G * 8, hipMemcpyHostToDevice, st));
-        }
-    }
-    (void)hipEventRecord(ctx->ev[EV_OUTPUT], st);
-    HIPCHK(hipStreamSynchronize(st));
-    mums_stats& s = ctx->st;
-    s = mums_stats{};
-    s.seedmers = Nall;
-    s.probes = P;
-    s.mem_count = M;
-    s.collision_count = C;
-    s.restarts = R;
-    s.repeat_limit_groups = R;
-    s.key_bytes = 8;
-    s.sort_passes = (uint64_t)((kbits + pbits + 7) / 8);
-    auto ms = [&](int a, int b) {
-        float f = 0;
-        return hipEventElapsedTime(&f, ctx->ev[a], ctx->ev[b]) == hipSuccess ? (double)f : 0.0;
-    };
-    s.ms_keys = ms(EV_START, EV_KEYS);
-    s.ms_sort = ms(EV_KEYS, EV_SORT);
-    s.ms_replay = ms(EV_SORT, EV_REPLAY);
-    s.ms_output = ms(EV_REPLAY, EV_OUTPUT);
-    s.ms_total = ms(EV_START, EV_OUTPUT);
-    return done(M, P);
-}
-
-int mums_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* probes, uint64_t* collisions, uint64_t* restarts) {
-    if (check_ctx(ctx)) return MUMS_E_INVALID;
-    if (!ctx->batch_result) return fail(ctx, MUMS_E_INVALID, "no completed mums_find_batch on this context");
-    if (match_off) std::copy(ctx->batch_off.begin(), ctx->batch_off.end(), match_off);
-    if (probes) std::copy(ctx->batch_probes.begin(), ctx->batch_probes.end(), probes);
-    if (collisions) std::copy(ctx->batch_coll.begin(), ctx->batch_coll.end(), collisions);
-    if (restarts) std::copy(ctx->batch_restarts.begin(), ctx->batch_restarts.end(), restarts);
-    return MUMS_OK;
-}
-
-// ---- mums_anchor_batch / mums_anchor_tail_batch: the whole of pairwiseAnchorSearch for B problems
-// (batch.hip's rounds on a carried table, anchor.hip's tail) ----
 // rows of one list the tail's lane takes; a longer list runs its tail through the single-list
 // path on the sub-context (mums_load_matches, v2, the filter).  DESIGN.md §5l has the measurement behind 1024.
 constexpr uint64_t kAnchorTailCap = 1024;
 
-static int anchor_sub(mums_ctx* ctx, const char* who) {
-    if (ctx->batch_sub) return MUMS_OK;
-    const int rc = mums_ctx_create(ctx->device, &ctx->batch_sub);
-    if (rc != MUMS_OK) return fail(ctx, rc, std::string(who) + ": no context for the single-problem pipeline");
-    return MUMS_OK;
+struct BatchRound {
+    uint64_t pat;
+    int L, w, kbits;
+    SeedSpec ss;
+};
+
+// the lists that are final on the host: routed[p], rcount[p] rows at rfirst[p] of rlen / rs
+struct BatchAlone {
+    std::vector<uint8_t> routed;
+    std::vector<uint64_t> rlen, rcount, rfirst;
+    std::vector<int64_t> rs;
+};
+
+struct BatchRun {
+    uint32_t B, G;
+    const char* ascii;
+    const uint64_t* seq_off;
+    bool carried;   // the rounds share a table and a tail follows (mums_anchor_batch)
+    std::vector<BatchRound> rd;
+    batch::Plan pl;
+    // bt_per: cnt, probes, coll, flag (B each), pool cursor; bt_seg: the plan's tables and doff
+    uint32_t *d_cnt, *d_probes, *d_coll, *d_flag, *d_pool_n;
+    uint64_t *d_aoff, *d_nlen, *d_doff;
+    uint32_t *d_mbase, *d_order, *d_obase, *d_ocap;
+    std::vector<uint32_t> per;   // bt_per's first 4 B words after the last round
+    int ev_round = EV_START;     // the event at the last round's start
+    double ms_keys = 0, ms_sort = 0, ms_replay = 0;   // of the rounds before the last
+};
+
+// what runs alone on the sub-context: a problem's sequences through `rounds` finds, or (rounds == 0)
+// a finished list; anchor: ClearSequences before every round, EliminateOverlaps_v2 and LengthFilter after
+struct AloneJob {
+    uint32_t G;
+    const char* ascii = nullptr;
+    const uint64_t* so = nullptr;
+    const uint64_t* patterns = nullptr;
+    uint32_t rounds = 0;
+    uint64_t n = 0;
+    const uint64_t* len = nullptr;
+    const int64_t* s = nullptr;
+    bool anchor = false;
+    int eliminate_both = 0;
+    uint64_t min_length = 0;
+};
+
+static double batch_ms(mums_ctx* ctx, int a, int b) {
+    float f = 0;
+    return hipEventElapsedTime(&f, ctx->ev[a], ctx->ev[b]) == hipSuccess ? (double)f : 0.0;
 }
 
-// the modes outside the batched scope, the same as mums_find_batch's
-static int anchor_refusals(mums_ctx* ctx, const std::string& who, uint32_t G) {
+static int batch_abort(mums_ctx* ctx, int rc) {
+    const std::string msg = ctx->err;
+    (void)mums_clear(ctx);
+    return fail(ctx, rc, msg);
+}
+
+// the modes outside the batched scope, before anything changes
+static int batch_refusals(mums_ctx* ctx, const std::string& who, uint32_t G) {
     if (ctx->shard || ctx->slice) return fail(ctx, MUMS_E_UNSUPPORTED, who + " on a sharded context");
     if (ctx->pairwise) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": PairwiseMatchFinder is not batched");
     if (ctx->pcompat) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": the ParallelMemHash compat mode is not batched");
@@ -3520,79 +3263,287 @@ static int anchor_refusals(mums_ctx* ctx, const std::string& who, uint32_t G) {
     return MUMS_OK;
 }
 
-// the sub-context's list appended to len / s
-static int anchor_take_rows(mums_ctx* sub, uint32_t G, std::vector<uint64_t>& len, std::vector<int64_t>& s, uint64_t* count) {
-    uint64_t M = 0;
-    int rc = mums_result_count(sub, &M, nullptr);
-    if (!rc && M) {
-        const size_t l0 = len.size(), s0 = s.size();
-        len.resize(l0 + M);
-        s.resize(s0 + M * (size_t)G);
-        rc = mums_result_copy(sub, len.data() + l0, s.data() + s0);
-    }
-    *count = M;
-    return rc;
+static int batch_sequences_check(mums_ctx* ctx, const std::string& who, uint32_t B, uint32_t G, const char* ascii,
+                                 const uint64_t* seq_off) {
+    if (batch::too_many_sequences(B, G)) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": more than 2^32 sequences");
+    if (B && !seq_off) return fail(ctx, MUMS_E_INVALID, who + ": null sequence offsets");
+    const uint64_t nseg = (uint64_t)B * G;
+    for (uint64_t s = 0; s < nseg; ++s)
+        if (seq_off[s + 1] < seq_off[s]) return fail(ctx, MUMS_E_INVALID, who + ": sequence offsets decrease");
+    if (B && seq_off[nseg] > seq_off[0] && !ascii) return fail(ctx, MUMS_E_INVALID, "Null gnSequence pointer");
+    return MUMS_OK;
 }
 
-// one list's tail alone on the sub-context; its surviving rows appended to rlen / rs
-static int anchor_tail_single(mums_ctx* ctx, const char* who, uint32_t G, uint64_t n, const uint64_t* len,
-                              const int64_t* s, int eliminate_both, uint64_t min_length, std::vector<uint64_t>& rlen,
-                              std::vector<int64_t>& rs, uint64_t* count) {
-    int rc = anchor_sub(ctx, who);
-    if (rc) return rc;
+static int batch_round(mums_ctx* ctx, uint64_t pat, BatchRound* x) {
+    x->pat = pat;
+    x->L = seed_len(pat);
+    x->w = __builtin_popcountll(pat);
+    if (x->L > 32) return fail(ctx, MUMS_E_INVALID, "Mer size is too large");
+    if (x->w > 31) return fail(ctx, MUMS_E_UNSUPPORTED, "seed weight 32 not supported");
+    x->kbits = 2 * x->w + 1;
+    x->ss = make_seed_spec(pat, x->L, x->w);
+    return MUMS_OK;
+}
+
+// The plan of run.rd's rounds.  cost: the size rule's constants, about lane_us per seed-mer of the
+// lanes' largest problem against alone_us per problem run alone
+static int batch_plan(mums_ctx* ctx, const std::string& who, BatchRun& run, batch::Cost cost) {
+    std::vector<batch::Round> rounds;
+    for (const BatchRound& x : run.rd) rounds.push_back({x.L, x.kbits});
+    run.pl = batch::make_plan(run.B, run.G, run.seq_off, rounds, batch_problem_cap(),
+                              getenv("MUMS_DEV_BATCH_NO_SPLIT") != nullptr, cost);
+    switch (run.pl.status) {
+    case batch::kTooManySequences: return fail(ctx, MUMS_E_UNSUPPORTED, who + ": more than 2^32 sequences");
+    case batch::kTooManySeedMers:
+        return fail(ctx, MUMS_E_UNSUPPORTED, who + ": 2^32 seed-mers or more in one " +
+                                                 (run.carried ? "round of the batch" : "batch") + " (split it)");
+    case batch::kTooManySlots:
+        return fail(ctx, MUMS_E_UNSUPPORTED, who + ": the rounds' tables need 2^32 slots or more (split the batch)");
+    default: return MUMS_OK;
+    }
+}
+
+// Carves bt_per and bt_seg, uploads the sequences and the plan's tables, and refuses a '-'
+static int batch_setup(mums_ctx* ctx, BatchRun& run) {
+    const uint32_t B = run.B, G = run.G;
+    const uint64_t nseg = (uint64_t)B * G, a0 = run.seq_off[0], A = run.seq_off[nseg] - a0;
+    const batch::Plan& pl = run.pl;
+    hipStream_t st = ctx->stream;
+    (void)hipEventRecord(ctx->ev[EV_START], st);
+    // per-problem device words: cnt, probes, coll, flag (B each), pool cursor, first '-' offset
+    HIPCHK(ctx->bt_per.ensure(((size_t)4 * B + 4) * 4 + 64));
+    run.d_cnt = ctx->bt_per.as<uint32_t>();
+    run.d_probes = run.d_cnt + B;
+    run.d_coll = run.d_cnt + 2 * (size_t)B;
+    run.d_flag = run.d_cnt + 3 * (size_t)B;
+    run.d_pool_n = run.d_cnt + 4 * (size_t)B;
+    unsigned long long* d_first = (unsigned long long*)(run.d_pool_n + 2);
+    HIPCHK(hipMemsetAsync(ctx->bt_per.p, 0, ((size_t)4 * B + 2) * 4, st));
+    HIPCHK(hipMemsetAsync(d_first, 0xFF, 8, st));
+    HIPCHK(ctx->bt_ascii.ensure(A + 64));
+    if (A) HIPCHK(hipMemcpyAsync(ctx->bt_ascii.p, run.ascii + a0, A, hipMemcpyHostToDevice, st));
+    // segment tables: aoff, nlen (nseg + 1 u64 each), doff (B u64), mbase (nseg + 1 u32; the rounds
+    // upload theirs), order, obase, ocap (B u32 each)
+    HIPCHK(ctx->bt_seg.ensure((2 * (nseg + 1) + B) * 8 + (nseg + 1 + 3 * (size_t)B) * 4 + 64));
+    run.d_aoff = ctx->bt_seg.as<uint64_t>();
+    run.d_nlen = run.d_aoff + nseg + 1;
+    run.d_doff = run.d_nlen + nseg + 1;
+    run.d_mbase = (uint32_t*)(run.d_doff + B);
+    run.d_order = run.d_mbase + nseg + 1;
+    run.d_obase = run.d_order + B;
+    run.d_ocap = run.d_obase + B;
+    // (order: problems of similar size share a wave; the ones run alone come first and have no seed-mers here)
+    HIPCHK(hipMemcpyAsync(run.d_aoff, pl.aoff.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(run.d_nlen, pl.nlen.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(run.d_order, pl.order.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    if (run.carried) {
+        HIPCHK(hipMemcpyAsync(run.d_obase, pl.obase.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(run.d_ocap, pl.ocap.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(launch_batch_gap(ctx->bt_ascii.as<char>(), 0, A, d_first, st));
+    unsigned long long first_gap = ~0ull;
+    HIPCHK(hipMemcpyAsync(&first_gap, d_first, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (first_gap == ~0ull) return MUMS_OK;
+    // SortedMerList.cpp:433-437 throws for the sequence holding it
+    const uint64_t s = (uint64_t)(std::upper_bound(run.seq_off, run.seq_off + nseg + 1, a0 + first_gap) - run.seq_off) - 1;
+    if (run.carried) (void)mums_clear(ctx);
+    else batch_vectors(ctx, 0, false);
+    return fail(ctx, MUMS_E_GAP, "Gap in genome sequence: problem " + std::to_string(s / G) + " of the batch");
+}
+
+// The lanes' rounds: keys, sort, replay per round, then run.per.  ord_words, pool_cap64: the sizes
+// of the table slices and of the entry pool, which the two modes state in their own terms
+static int batch_rounds(mums_ctx* ctx, BatchRun& run, uint64_t ord_words, uint64_t pool_cap64) {
+    const uint32_t B = run.B, G = run.G;
+    const uint64_t nseg = (uint64_t)B * G;
+    const batch::Plan& pl = run.pl;
+    const int pbits = batch::ceil_log2(B);
+    hipStream_t st = ctx->stream;
+    run.per.assign((size_t)4 * B, 0);
+    if (pl.Nmax == 0) {
+        (void)hipEventRecord(ctx->ev[EV_KEYS], st);
+        (void)hipEventRecord(ctx->ev[EV_SORT], st);
+        (void)hipEventRecord(ctx->ev[EV_REPLAY], st);
+        return MUMS_OK;
+    }
+    HIPCHK(ctx->bt_keys.ensure(pl.Nmax * 8 + 64));
+    HIPCHK(ctx->bt_kA.ensure(pl.Nmax * 8 + 64));
+    HIPCHK(ctx->bt_kB.ensure(pl.Nmax * 8 + 64));
+    HIPCHK(ctx->bt_vA.ensure(pl.Nmax * 4 + 64));
+    HIPCHK(ctx->bt_vB.ensure(pl.Nmax * 4 + 64));
+    HIPCHK(ctx->bt_tmp.ensure(radix_tmp_bytes(pl.Nmax) + 256));
+    HIPCHK(ctx->bt_ord.ensure(ord_words * 8));
+    HIPCHK(ctx->bt_pool.ensure(pool_cap64 * (size_t)(G + 2) * 8 + 64));
+    for (size_t r = 0; r < run.rd.size(); ++r) {
+        const BatchRound& x = run.rd[r];
+        const uint64_t N = pl.N[r];
+        // the keys built and sorted below hold the problem id above the canonical key: the plan gives
+        // the lanes no record when that does not fit
+        const int kbits = x.kbits;
+        const bool lanes = kbits + pbits <= 64;
+        if (N > 0 && !lanes) return fail(ctx, MUMS_E_UNSUPPORTED, "batched sort keys wider than 64 bits reached the lanes");
+        if (r > 0) {
+            (void)hipEventRecord(ctx->ev[EV_GROUPS], st);
+            run.ev_round = EV_GROUPS;
+        }
+        if (N > 0) {
+            HIPCHK(hipMemcpyAsync(run.d_mbase, pl.mbase[r].data(), (nseg + 1) * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(launch_batch_keys(ctx->bt_ascii.as<char>(), run.d_aoff, run.d_mbase, (uint32_t)nseg, G, (uint32_t)N, x.ss,
+                                     x.kbits, ctx->bt_keys.as<uint64_t>(), st));
+        }
+        (void)hipEventRecord(ctx->ev[EV_KEYS], st);
+        int ob = 0;
+        if (N > 0)
+            HIPCHK(radix_sort<uint64_t>(ctx->bt_keys.as<uint64_t>(), nullptr, N, x.kbits + pbits, ctx->bt_kA.as<uint64_t>(),
+                                        ctx->bt_vA.as<uint32_t>(), ctx->bt_kB.as<uint64_t>(), ctx->bt_vB.as<uint32_t>(),
+                                        ctx->bt_tmp.p, &ob, st));
+        (void)hipEventRecord(ctx->ev[EV_SORT], st);
+        if (N > 0) {
+            BatchReplay br{};
+            br.sk = ob == 0 ? ctx->bt_kA.as<uint64_t>() : ctx->bt_kB.as<uint64_t>();
+            br.sv = ob == 0 ? ctx->bt_vA.as<uint32_t>() : ctx->bt_vB.as<uint32_t>();
+            br.keys = ctx->bt_keys.as<uint64_t>();
+            br.mbase = run.d_mbase;
+            br.nlen = run.d_nlen;
+            br.order = run.d_order;
+            br.ord = ctx->bt_ord.as<uint64_t>();
+            br.pool = ctx->bt_pool.as<int64_t>();
+            br.pool_cap = (uint32_t)pool_cap64;
+            br.pool_n = run.d_pool_n;
+            br.cnt = run.d_cnt;
+            br.probes = run.d_probes;
+            br.coll = run.d_coll;
+            br.flag = run.d_flag;
+            br.B = B;
+            br.G = G;
+            br.L = x.L;
+            br.kbits = x.kbits;
+            br.table_size = ctx->table_size;
+            br.masked = ctx->masked;
+            br.seq_mask = ctx->seq_mask;
+            if (run.carried) {   // else the single-round kernel, a problem's slice at mbase[p * G] / 2
+                br.ord_base = run.d_obase;
+                br.ord_cap = run.d_ocap;
+            }
+            HIPCHK(launch_batch_replay(br, st));
+        }
+        (void)hipEventRecord(ctx->ev[EV_REPLAY], st);
+        const bool last = r + 1 == run.rd.size();
+        if (last) HIPCHK(hipMemcpyAsync(run.per.data(), run.d_cnt, (size_t)4 * B * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));   // the next round's mbase replaces this one's; the phase times
+        if (last) break;                    // (batch_stats reads the last round's)
+        run.ms_keys += batch_ms(ctx, run.ev_round, EV_KEYS);
+        run.ms_sort += batch_ms(ctx, EV_KEYS, EV_SORT);
+        run.ms_replay += batch_ms(ctx, EV_SORT, EV_REPLAY);
+    }
+    return MUMS_OK;
+}
+
+// job alone on the sub-context, as list p of al; a problem's counters go to the context's vectors:
+// probes and restarts summed over the rounds, the collisions of the last find (cumulative on a
+// kept table), the table's entries before the tail
+static int batch_alone(mums_ctx* ctx, const std::string& who, const AloneJob& j, BatchAlone& al, uint32_t p) {
+    if (!ctx->batch_sub) {
+        const int rc = mums_ctx_create(ctx->device, &ctx->batch_sub);
+        if (rc != MUMS_OK) return fail(ctx, rc, who + ": no context for the single-problem pipeline");
+    }
     mums_ctx* sub = ctx->batch_sub;
-    rc = mums_clear(sub);
-    if (!rc) rc = mums_load_matches(sub, G, n, len, s);
-    if (!rc) rc = mums_eliminate_overlaps_v2(sub, nullptr, 0, eliminate_both);
-    if (!rc) rc = mums_length_filter(sub, min_length);
-    if (!rc) rc = anchor_take_rows(sub, G, rlen, rs, count);
-    if (rc) return fail(ctx, rc, std::string(who) + ", single-list tail: " + sub->err);
+    int rc = mums_clear(sub);
+    if (!rc && j.rounds) rc = mums_set_params(sub, 0, 1, ctx->table_size);
+    if (!rc && j.rounds) rc = mums_set_mask(sub, ctx->masked, ctx->seq_mask);
+    for (uint32_t r = 0; r < j.rounds && !rc; ++r) {
+        if (j.anchor) rc = mums_clear_sequences(sub);
+        if (!rc) rc = mums_set_seed(sub, j.patterns[r]);
+        for (uint32_t g = 0; g < j.G && !rc; ++g) rc = mums_add_genome(sub, j.ascii + j.so[g], j.so[g + 1] - j.so[g]);
+        if (!rc) rc = mums_find(sub);
+        if (!rc) {
+            ctx->batch_probes[p] += sub->st.probes;
+            ctx->batch_coll[p] = sub->st.collision_count;
+            ctx->batch_restarts[p] += sub->st.restarts;
+        }
+    }
+    if (!rc && j.rounds) rc = mums_result_count(sub, &ctx->anchor_table[p], nullptr);
+    if (!rc && !j.rounds) rc = mums_load_matches(sub, j.G, j.n, j.len, j.s);
+    if (!rc && j.anchor) rc = mums_eliminate_overlaps_v2(sub, nullptr, 0, j.eliminate_both);
+    if (!rc && j.anchor) rc = mums_length_filter(sub, j.min_length);
+    uint64_t M = 0;
+    if (!rc) rc = mums_result_count(sub, &M, nullptr);
+    al.rfirst[p] = al.rlen.size();
+    if (!rc && M) {
+        al.rlen.resize(al.rlen.size() + M);
+        al.rs.resize(al.rs.size() + M * (size_t)j.G);
+        rc = mums_result_copy(sub, al.rlen.data() + al.rfirst[p], al.rs.data() + al.rfirst[p] * j.G);
+    }
+    if (rc) return fail(ctx, rc, who + (j.rounds ? ", single-problem pipeline: " : ", single-list tail: ") + sub->err);
+    al.rcount[p] = M;
+    al.routed[p] = 1;
     (void)mums_clear(sub);
     return MUMS_OK;
 }
 
-// problem p's whole pairwiseAnchorSearch alone on the sub-context: Clear; per round ClearSequences,
-// the round's seed, the sequences, FindMatches; EliminateOverlaps_v2; LengthFilter
-static int anchor_single(mums_ctx* ctx, uint32_t G, const char* ascii, const uint64_t* so, const uint64_t* patterns,
-                         uint32_t rounds, int eliminate_both, uint64_t min_length, std::vector<uint64_t>& rlen,
-                         std::vector<int64_t>& rs, uint64_t* count, uint64_t* table, uint64_t* probes, uint64_t* coll,
-                         uint64_t* restarts) {
-    int rc = anchor_sub(ctx, "mums_anchor_batch");
-    if (rc) return rc;
-    mums_ctx* sub = ctx->batch_sub;
-    rc = mums_clear(sub);
-    if (!rc) rc = mums_set_params(sub, 0, 1, ctx->table_size);
-    if (!rc) rc = mums_set_mask(sub, ctx->masked, ctx->seq_mask);
-    *probes = *coll = *restarts = *table = 0;
-    for (uint32_t r = 0; r < rounds && !rc; ++r) {
-        rc = mums_clear_sequences(sub);
-        if (!rc) rc = mums_set_seed(sub, patterns[r]);
-        for (uint32_t g = 0; g < G && !rc; ++g) rc = mums_add_genome(sub, ascii + so[g], so[g + 1] - so[g]);
-        if (!rc) rc = mums_find(sub);
-        if (!rc) {
-            *probes += sub->st.probes;
-            *coll = sub->st.collision_count;   // cumulative over a kept table's finds
-            *restarts += sub->st.restarts;
+// The lanes' counters; the problems left out (above the cap, the size rule) or not finished in some
+// round (MER_REPEAT_LIMIT, pool) run alone, from round 0.  job: what every such problem shares
+static int batch_fallbacks(mums_ctx* ctx, const std::string& who, BatchRun& run, AloneJob job, BatchAlone& al) {
+    const uint32_t B = run.B;
+    const uint32_t *h_cnt = run.per.data(), *h_probes = h_cnt + B, *h_coll = h_cnt + 2 * (size_t)B, *h_flag = h_cnt + 3 * (size_t)B;
+    al.routed = run.pl.routed;
+    al.rcount.assign(B, 0);
+    al.rfirst.assign(B, 0);
+    for (uint32_t p = 0; p < B; ++p) {
+        if (!al.routed[p] && !h_flag[p]) {
+            ctx->batch_probes[p] = h_probes[p];
+            ctx->batch_coll[p] = h_coll[p];
+            ctx->anchor_table[p] = h_cnt[p];
+            continue;
         }
+        job.so = run.seq_off + (uint64_t)p * run.G;
+        const int rc = batch_alone(ctx, who, job, al, p);
+        if (rc) return rc;
     }
-    if (!rc) rc = mums_result_count(sub, table, nullptr);
-    if (!rc) rc = mums_eliminate_overlaps_v2(sub, nullptr, 0, eliminate_both);
-    if (!rc) rc = mums_length_filter(sub, min_length);
-    if (!rc) rc = anchor_take_rows(sub, G, rlen, rs, count);
-    if (rc) return fail(ctx, rc, std::string("mums_anchor_batch, single-problem pipeline: ") + sub->err);
-    (void)mums_clear(sub);
+    HIPCHK(hipSetDevice(ctx->device));
+    return MUMS_OK;
+}
+
+// The context's MatchList: list p has al.rcount[p] rows if it is final on the host, else h_cnt[p].
+// Sets ctx->batch_off; emit (empty: no lane ran) writes the lanes' rows once doff is at d_doff,
+// the host's rows are copied into place
+static int batch_output(mums_ctx* ctx, uint32_t B, uint32_t G, const BatchAlone& al, const uint32_t* h_cnt,
+                        uint64_t* d_doff, const std::function<hipError_t()>& emit, uint64_t* M_out) {
+    hipStream_t st = ctx->stream;
+    uint64_t M = 0;
+    std::vector<uint64_t> doff(B);
+    for (uint32_t p = 0; p < B; ++p) {
+        ctx->batch_off[p] = doff[p] = M;
+        M += al.routed[p] ? al.rcount[p] : h_cnt[p];
+    }
+    ctx->batch_off[B] = M;
+    HIPCHK(ctx->out_len.ensure((M + 1) * 8));
+    HIPCHK(ctx->out_s.ensure((M + 1) * (size_t)G * 8 + 8));
+    if (M > 0 && emit) {
+        HIPCHK(hipMemcpyAsync(d_doff, doff.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(emit());
+    }
+    for (uint32_t p = 0; p < B; ++p) {
+        if (!al.routed[p] || al.rcount[p] == 0) continue;
+        HIPCHK(hipMemcpyAsync(ctx->out_len.as<uint64_t>() + doff[p], al.rlen.data() + al.rfirst[p], al.rcount[p] * 8,
+                              hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->out_s.as<int64_t>() + doff[p] * G, al.rs.data() + al.rfirst[p] * G,
+                              al.rcount[p] * (size_t)G * 8, hipMemcpyHostToDevice, st));
+    }
+    (void)hipEventRecord(ctx->ev[EV_OUTPUT], st);
+    HIPCHK(hipStreamSynchronize(st));
+    *M_out = M;
     return MUMS_OK;
 }
 
 // The tail of every list and the context's MatchList.  List p has toff[p + 1] - toff[p] rows; fill()
-// puts them into the work arrays (d_toff, d_wlen, d_ws) on the context's stream.  routed[p]: the
-// list is final already, rcount[p] rows at rfirst[p] of rlen / rs.  A list above kAnchorTailCap
-// runs alone and joins the routed ones.  Sets ctx->batch_off and *M_out.
+// puts them into the work arrays (d_toff, d_wlen, d_ws) on the context's stream.  A list of al is
+// final already.  A list above kAnchorTailCap runs alone and joins them.
 using AnchorFill = std::function<hipError_t(uint64_t*, int64_t*, int64_t*)>;
-static int anchor_tail_stage(mums_ctx* ctx, const char* who, uint32_t B, uint32_t G, const std::vector<uint64_t>& toff,
-                             std::vector<uint8_t>& routed, std::vector<uint64_t>& rlen, std::vector<int64_t>& rs,
-                             std::vector<uint64_t>& rcount, std::vector<uint64_t>& rfirst, int eliminate_both,
-                             uint64_t min_length, const AnchorFill& fill, uint64_t* M_out) {
+static int anchor_tail_stage(mums_ctx* ctx, const std::string& who, uint32_t B, uint32_t G, const std::vector<uint64_t>& toff,
+                             BatchAlone& al, int eliminate_both, uint64_t min_length, const AnchorFill& fill,
+                             uint64_t* M_out) {
     hipStream_t st = ctx->stream;
     const uint64_t Tt = toff[B];
     // toff (B + 1 u64), doff (B u64), cnt (B u32), order (B u32), skip (B bytes)
@@ -3609,27 +3560,31 @@ static int anchor_tail_stage(mums_ctx* ctx, const char* who, uint32_t B, uint32_
     HIPCHK(hipMemcpyAsync(d_toff, toff.data(), ((size_t)B + 1) * 8, hipMemcpyHostToDevice, st));
     {
         const hipError_t e = fill(d_toff, ctx->an_wlen.as<int64_t>(), ctx->an_ws.as<int64_t>());
-        if (e != hipSuccess) return fail(ctx, MUMS_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+        if (e != hipSuccess) return fail(ctx, MUMS_E_HIP, who + ": " + hipGetErrorString(e));
     }
-    std::vector<uint8_t> skip(routed);
     std::vector<uint64_t> big_len;
     std::vector<int64_t> big_s;
     for (uint32_t p = 0; p < B; ++p) {
         const uint64_t n = toff[p + 1] - toff[p];
-        if (routed[p] || n <= kAnchorTailCap) continue;
+        if (al.routed[p] || n <= kAnchorTailCap) continue;
         big_len.resize(n);
         big_s.resize(n * (size_t)G);
         HIPCHK(hipMemcpyAsync(big_len.data(), ctx->an_wlen.as<int64_t>() + toff[p], n * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(big_s.data(), ctx->an_ws.as<int64_t>() + toff[p] * G, n * (size_t)G * 8,
                               hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        rfirst[p] = rlen.size();
-        const int rc = anchor_tail_single(ctx, who, G, n, big_len.data(), big_s.data(), eliminate_both, min_length, rlen,
-                                          rs, &rcount[p]);
+        AloneJob job{G};
+        job.n = n;
+        job.len = big_len.data();
+        job.s = big_s.data();
+        job.anchor = true;
+        job.eliminate_both = eliminate_both;
+        job.min_length = min_length;
+        const int rc = batch_alone(ctx, who, job, al, p);
         if (rc) return rc;
         HIPCHK(hipSetDevice(ctx->device));
-        routed[p] = skip[p] = 1;
     }
+    const std::vector<uint8_t>& skip = al.routed;
     std::vector<uint32_t> order(B);
     for (uint32_t p = 0; p < B; ++p) order[p] = p;
     std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
@@ -3654,50 +3609,118 @@ static int anchor_tail_stage(mums_ctx* ctx, const char* who, uint32_t B, uint32_
     std::vector<uint32_t> h_cnt(B, 0);
     HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    uint64_t M = 0;
-    std::vector<uint64_t> doff(B);
-    for (uint32_t p = 0; p < B; ++p) {
-        ctx->batch_off[p] = M;
-        doff[p] = M;
-        M += routed[p] ? rcount[p] : h_cnt[p];
-    }
-    ctx->batch_off[B] = M;
-    HIPCHK(ctx->out_len.ensure((M + 1) * 8));
-    HIPCHK(ctx->out_s.ensure((M + 1) * (size_t)G * 8 + 8));
-    if (M > 0) {
-        HIPCHK(hipMemcpyAsync(d_doff, doff.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(launch_anchor_emit(at.V, at.wlen, at.ws, d_toff, d_cnt, d_doff, B, G, ctx->out_len.as<uint64_t>(),
-                                  ctx->out_s.as<int64_t>(), st));
-        for (uint32_t p = 0; p < B; ++p) {
-            if (!routed[p] || rcount[p] == 0) continue;
-            HIPCHK(hipMemcpyAsync(ctx->out_len.as<uint64_t>() + doff[p], rlen.data() + rfirst[p], rcount[p] * 8,
-                                  hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(ctx->out_s.as<int64_t>() + doff[p] * G, rs.data() + rfirst[p] * G,
-                                  rcount[p] * (size_t)G * 8, hipMemcpyHostToDevice, st));
-        }
-    }
-    (void)hipEventRecord(ctx->ev[EV_OUTPUT], st);
-    HIPCHK(hipStreamSynchronize(st));
-    *M_out = M;
-    return MUMS_OK;
+    return batch_output(ctx, B, G, al, h_cnt.data(), d_doff, [&] {
+        return launch_anchor_emit(at.V, at.wlen, at.ws, d_toff, d_cnt, d_doff, B, G, ctx->out_len.as<uint64_t>(),
+                                  ctx->out_s.as<int64_t>(), st);
+    }, M_out);
 }
 
-static float anchor_ms(mums_ctx* ctx, int a, int b) {
-    float f = 0;
-    return hipEventElapsedTime(&f, ctx->ev[a], ctx->ev[b]) == hipSuccess ? f : 0.0f;
+// mums_get_stats of a batch: the per-problem counters' sums, the rounds' seed-mers, sort passes and phase times
+static void batch_stats(mums_ctx* ctx, const BatchRun& run, uint64_t mem_count) {
+    mums_stats& s = ctx->st;
+    s = mums_stats{};
+    for (uint32_t p = 0; p < run.B; ++p) {
+        s.probes += ctx->batch_probes[p];
+        s.collision_count += ctx->batch_coll[p];
+        s.restarts += ctx->batch_restarts[p];
+    }
+    s.repeat_limit_groups = s.restarts;
+    s.mem_count = mem_count;
+    s.key_bytes = 8;
+    for (size_t r = 0; r < run.rd.size(); ++r) {
+        s.seedmers += run.pl.Nall[r];
+        s.sort_passes += (uint64_t)((run.rd[r].kbits + batch::ceil_log2(run.B) + 7) / 8);
+    }
+    s.ms_keys = run.ms_keys + batch_ms(ctx, run.ev_round, EV_KEYS);
+    s.ms_sort = run.ms_sort + batch_ms(ctx, EV_KEYS, EV_SORT);
+    s.ms_replay = run.ms_replay + batch_ms(ctx, EV_SORT, EV_REPLAY);
+    s.ms_output = batch_ms(ctx, EV_REPLAY, EV_OUTPUT);
+    s.ms_total = batch_ms(ctx, EV_START, EV_OUTPUT);
 }
 
-// the context holds a finished anchor batch: one MatchList, the problems' lists in order
-static int anchor_done(mums_ctx* ctx, uint32_t G, uint64_t M, uint64_t P, uint64_t N) {
+// the context holds a finished batch: one MatchList of M rows, the problems' lists in order
+static int batch_done(mums_ctx* ctx, uint32_t G, uint64_t M, bool anchor) {
     ctx->gt = GenomeTable{};
     ctx->gt.G = (int)G;
     ctx->M = M;
-    ctx->P = P;
-    ctx->N = N;
+    ctx->P = ctx->st.probes;
+    ctx->N = ctx->st.seedmers;
     ctx->batch_result = true;
-    ctx->anchor_result = true;
+    ctx->anchor_result = anchor;
     ctx->list_edited = true;
     ctx->stage_done = MUMS_STAGE_ALL;
+    return MUMS_OK;
+}
+
+static void batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* table_entries, uint64_t* probes, uint64_t* collisions,
+                       uint64_t* restarts) {
+    if (match_off) std::copy(ctx->batch_off.begin(), ctx->batch_off.end(), match_off);
+    if (table_entries) std::copy(ctx->anchor_table.begin(), ctx->anchor_table.end(), table_entries);
+    if (probes) std::copy(ctx->batch_probes.begin(), ctx->batch_probes.end(), probes);
+    if (collisions) std::copy(ctx->batch_coll.begin(), ctx->batch_coll.end(), collisions);
+    if (restarts) std::copy(ctx->batch_restarts.begin(), ctx->batch_restarts.end(), restarts);
+}
+
+int mums_find_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const char* ascii, const uint64_t* seq_off) {
+    if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (!have_device()) return fail(ctx, MUMS_E_NODEVICE, "no HIP device");
+    const std::string who = "mums_find_batch";
+    int rc = batch_refusals(ctx, who, G);
+    if (rc) return rc;
+    if (ctx->seed == 0) return fail(ctx, MUMS_E_INVALID, "mums_find_batch: the seed pattern must be set (mums_set_seed)");
+    rc = batch_sequences_check(ctx, who, B, G, ascii, seq_off);
+    if (rc) return rc;
+    BatchRun run{B, G, ascii, seq_off, false};
+    run.rd.resize(1);
+    const BatchRound& x = run.rd[0];
+    rc = batch_round(ctx, ctx->seed, &run.rd[0]);
+    if (!rc) rc = batch_plan(ctx, who, run, {10.0, 1000.0});   // kLaneUs, kSingleUs
+    if (rc) return rc;
+
+    // starts as MemHash::Clear does
+    rc = mums_clear(ctx);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->pattern = x.pat;
+    ctx->L = x.L;
+    ctx->w = x.w;
+    ctx->ss = x.ss;
+    ctx->gt = GenomeTable{};
+    ctx->gt.G = (int)G;
+    batch_vectors(ctx, B, true);
+    if (B == 0) return batch_done(ctx, G, 0, false);
+
+    rc = batch_setup(ctx, run);
+    if (rc) return rc;
+    // a problem's table is in ord at half its first record's index; the entry pool
+    const uint64_t N = run.pl.N[0];
+    const uint64_t pool_cap64 = std::min<uint64_t>(N / 2 + 1, std::max<uint64_t>(N / 8, 1ull << 16));
+    rc = batch_rounds(ctx, run, N / 2 + 2, pool_cap64);
+    if (rc) return rc;
+    AloneJob job{G};
+    job.ascii = ascii;
+    job.patterns = &ctx->seed;
+    job.rounds = 1;
+    BatchAlone al;
+    rc = batch_fallbacks(ctx, who, run, job, al);
+    if (rc) return batch_abort(ctx, rc);
+    std::function<hipError_t()> emit;
+    if (N > 0)
+        emit = [&] {
+            return launch_batch_emit(ctx->bt_ord.as<uint64_t>(), ctx->bt_pool.as<int64_t>(), run.d_mbase, run.d_cnt,
+                                     run.d_doff, B, G, ctx->out_len.as<uint64_t>(), ctx->out_s.as<int64_t>(), ctx->stream);
+        };
+    uint64_t M = 0;
+    rc = batch_output(ctx, B, G, al, run.per.data(), run.d_doff, emit, &M);
+    if (rc) return rc;
+    batch_stats(ctx, run, M);
+    return batch_done(ctx, G, M, false);
+}
+
+int mums_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* probes, uint64_t* collisions, uint64_t* restarts) {
+    if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (!ctx->batch_result) return fail(ctx, MUMS_E_INVALID, "no completed mums_find_batch on this context");
+    batch_info(ctx, match_off, nullptr, probes, collisions, restarts);
     return MUMS_OK;
 }
 
@@ -3705,7 +3728,6 @@ int mums_anchor_tail_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const uint64_t
                            const int64_t* starts, int eliminate_both, uint64_t min_length) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
     if (!have_device()) return fail(ctx, MUMS_E_NODEVICE, "no HIP device");
-    const char* who = "mums_anchor_tail_batch";
     if (ctx->shard || ctx->slice) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_anchor_tail_batch on a sharded context");
     if (G < 1) return fail(ctx, MUMS_E_INVALID, "mums_anchor_tail_batch: no sequences");
     if (G > (uint32_t)kMaxG) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_anchor_tail_batch: more than 64 sequences per list");
@@ -3718,20 +3740,17 @@ int mums_anchor_tail_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const uint64_t
     int rc = mums_clear(ctx);
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    ctx->batch_off.assign((size_t)B + 1, 0);
-    ctx->batch_probes.assign(B, 0);
-    ctx->batch_coll.assign(B, 0);
-    ctx->batch_restarts.assign(B, 0);
-    ctx->anchor_table.assign(B, 0);
-    if (B == 0) return anchor_done(ctx, G, 0, 0, 0);
+    batch_vectors(ctx, B, true);
+    if (B == 0) return batch_done(ctx, G, 0, true);
     hipStream_t st = ctx->stream;
     (void)hipEventRecord(ctx->ev[EV_START], st);
     std::vector<uint64_t> toff((size_t)B + 1);
     for (uint32_t p = 0; p <= B; ++p) toff[p] = match_off[p] - r0;
     for (uint32_t p = 0; p < B; ++p) ctx->anchor_table[p] = toff[p + 1] - toff[p];
-    std::vector<uint8_t> routed(B, 0);
-    std::vector<uint64_t> rlen, rcount(B, 0), rfirst(B, 0);
-    std::vector<int64_t> rs;
+    BatchAlone al;
+    al.routed.assign(B, 0);
+    al.rcount.assign(B, 0);
+    al.rfirst.assign(B, 0);
     auto fill = [&](uint64_t*, int64_t* d_wlen, int64_t* d_ws) -> hipError_t {
         hipError_t e = hipSuccess;
         if (Tt) e = hipMemcpyAsync(d_wlen, lengths + r0, Tt * 8, hipMemcpyHostToDevice, st);
@@ -3740,309 +3759,78 @@ int mums_anchor_tail_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const uint64_t
         return e;
     };
     uint64_t M = 0;
-    rc = anchor_tail_stage(ctx, who, B, G, toff, routed, rlen, rs, rcount, rfirst, eliminate_both, min_length, fill, &M);
-    if (rc) {
-        const std::string msg = ctx->err;
-        (void)mums_clear(ctx);
-        return fail(ctx, rc, msg);
-    }
+    rc = anchor_tail_stage(ctx, "mums_anchor_tail_batch", B, G, toff, al, eliminate_both, min_length, fill, &M);
+    if (rc) return batch_abort(ctx, rc);
     mums_stats& s = ctx->st;
     s = mums_stats{};
     s.mem_count = Tt;
-    s.ms_keys = anchor_ms(ctx, EV_START, EV_KEYS);
-    s.ms_output = anchor_ms(ctx, EV_KEYS, EV_OUTPUT);
-    s.ms_total = anchor_ms(ctx, EV_START, EV_OUTPUT);
-    return anchor_done(ctx, G, M, 0, 0);
+    s.ms_keys = batch_ms(ctx, EV_START, EV_KEYS);
+    s.ms_output = batch_ms(ctx, EV_KEYS, EV_OUTPUT);
+    s.ms_total = batch_ms(ctx, EV_START, EV_OUTPUT);
+    return batch_done(ctx, G, M, true);
 }
 
 int mums_anchor_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const char* ascii, const uint64_t* seq_off,
                       const uint64_t* patterns, uint32_t rounds, int eliminate_both, uint64_t min_length) {
     if (check_ctx(ctx)) return MUMS_E_INVALID;
     if (!have_device()) return fail(ctx, MUMS_E_NODEVICE, "no HIP device");
-    const char* who = "mums_anchor_batch";
-    // modes outside the batched scope, before anything changes
-    int rc = anchor_refusals(ctx, who, G);
+    const std::string who = "mums_anchor_batch";
+    int rc = batch_refusals(ctx, who, G);
     if (rc) return rc;
     if (rounds < 1 || rounds > 8) return fail(ctx, MUMS_E_INVALID, "mums_anchor_batch: 1 to 8 rounds");
     if (!patterns) return fail(ctx, MUMS_E_INVALID, "mums_anchor_batch: null seed patterns");
-    const uint64_t nseg = (uint64_t)B * G;
-    const int pbits = ceil_log2(B ? B : 1);
-    struct Round {
-        uint64_t pat;
-        int L, w, kbits;
-        SeedSpec ss;
-        uint64_t Nall = 0, N = 0;
-        std::vector<uint32_t> mbase;
-    };
-    std::vector<Round> rd(rounds);
-    bool lanes = true;
+    BatchRun run{B, G, ascii, seq_off, true};
+    run.rd.resize(rounds);
     for (uint32_t r = 0; r < rounds; ++r) {
-        Round& x = rd[r];
-        x.pat = patterns[r];
-        if (x.pat == 0) return fail(ctx, MUMS_E_INVALID, "mums_anchor_batch: a seed pattern is 0");
-        x.L = seed_len(x.pat);
-        x.w = __builtin_popcountll(x.pat);
-        if (x.L > 32) return fail(ctx, MUMS_E_INVALID, "Mer size is too large");
-        if (x.w > 31) return fail(ctx, MUMS_E_UNSUPPORTED, "seed weight 32 not supported");
-        x.kbits = 2 * x.w + 1;
-        x.ss = make_seed_spec(x.pat, x.L, x.w);
-        lanes = lanes && x.kbits + pbits <= 64;
+        if (patterns[r] == 0) return fail(ctx, MUMS_E_INVALID, "mums_anchor_batch: a seed pattern is 0");
+        rc = batch_round(ctx, patterns[r], &run.rd[r]);
+        if (rc) return rc;
     }
-    if (nseg + 1 >= (1ull << 32)) return fail(ctx, MUMS_E_UNSUPPORTED, "mums_anchor_batch: more than 2^32 sequences");
-    if (B && !seq_off) return fail(ctx, MUMS_E_INVALID, "mums_anchor_batch: null sequence offsets");
-    for (uint64_t s = 0; s < nseg; ++s)
-        if (seq_off[s + 1] < seq_off[s]) return fail(ctx, MUMS_E_INVALID, "mums_anchor_batch: sequence offsets decrease");
-    const uint64_t a0 = B ? seq_off[0] : 0, A = B ? seq_off[nseg] - a0 : 0;
-    if (A && !ascii) return fail(ctx, MUMS_E_INVALID, "Null gnSequence pointer");
-    // the sequences' seed-mers per round; the lanes take every problem up to the cap in every round
-    const uint64_t cap = batch_problem_cap();
-    std::vector<uint8_t> routed(B, 0);
-    std::vector<uint64_t> recs((size_t)B * rounds, 0), tot(B, 0);   // recs[r * B + p]
-    for (uint32_t r = 0; r < rounds; ++r) {
-        const uint64_t L = (uint64_t)rd[r].L;
-        for (uint32_t p = 0; p < B; ++p) {
-            uint64_t k = 0;
-            for (uint32_t g = 0; g < G; ++g) {
-                const uint64_t n = seq_off[(uint64_t)p * G + g + 1] - seq_off[(uint64_t)p * G + g];
-                k += n < L ? 0 : n - L + 1;
-            }
-            recs[(size_t)r * B + p] = k;
-            tot[p] += k;
-            rd[r].Nall += k;
-            if (!lanes || k > cap) routed[p] = 1;
-            if (rd[r].Nall >= 0xFFFFFFF0ull)
-                return fail(ctx, MUMS_E_UNSUPPORTED, "mums_anchor_batch: 2^32 seed-mers or more in one round of the batch (split it)");
-        }
-    }
-    // The size rule of mums_find_batch in this path's terms: the lanes' pass lasts
-    // as long as its largest problem, about kLaneUs per seed-mer of all its rounds; a problem run
-    // alone costs about kSingleUs per round plus kTailUs for its tail.  The k largest run alone.
-    std::vector<uint32_t> order(B);
-    for (uint32_t p = 0; p < B; ++p) order[p] = p;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-        return (routed[x] ? ~0ull : tot[x]) > (routed[y] ? ~0ull : tot[y]);
-    });
-    if (lanes && !getenv("MUMS_DEV_BATCH_NO_SPLIT")) {
-        constexpr double kLaneUs = 18.0, kSingleUs = 915.0, kTailUs = 380.0;   // measured: DESIGN.md §5l
-        uint32_t k0 = 0, best = 0;
-        while (k0 < B && routed[order[k0]]) ++k0;
-        double best_cost = -1;
-        for (uint32_t k = k0; k <= B; ++k) {
-            const double cost = kLaneUs * (double)(k < B ? tot[order[k]] : 0) +
-                                (kSingleUs * (double)rounds + kTailUs) * (double)(k - k0);
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = k; }
-        }
-        for (uint32_t k = k0; k < best; ++k) routed[order[k]] = 1;
-    }
-    std::vector<uint64_t> aoff(nseg + 1, 0), nlen(nseg + 1, 0);
-    for (uint64_t s = 0; s < nseg; ++s) {
-        aoff[s] = seq_off[s] - a0;
-        nlen[s] = seq_off[s + 1] - seq_off[s];
-    }
-    uint64_t Nmax = 0, Nsum = 0;
-    for (uint32_t r = 0; r < rounds; ++r) {
-        Round& x = rd[r];
-        x.mbase.assign(nseg + 1, 0);
-        for (uint64_t s = 0; s < nseg; ++s) {
-            x.mbase[s] = (uint32_t)x.N;
-            if (!routed[s / G]) x.N += nlen[s] < (uint64_t)x.L ? 0 : nlen[s] - x.L + 1;
-        }
-        x.mbase[nseg] = (uint32_t)x.N;
-        Nmax = std::max(Nmax, x.N);
-        Nsum += x.N;
-    }
-    // problem p's slice of ord: an entry needs a probe and a probe two records of its round, so the
-    // table after the last round has at most the sum over the rounds of half the round's records
-    std::vector<uint32_t> obase(B, 0), ocap(B, 0);
-    uint64_t ord_words = 0;
-    for (uint32_t p = 0; p < B; ++p) {
-        uint64_t c = 0;
-        for (uint32_t r = 0; r < rounds && !routed[p]; ++r) c += recs[(size_t)r * B + p] >> 1;
-        if (ord_words + c >= 0xFFFFFFF0ull)
-            return fail(ctx, MUMS_E_UNSUPPORTED, "mums_anchor_batch: the rounds' tables need 2^32 slots or more (split the batch)");
-        obase[p] = (uint32_t)ord_words;
-        ocap[p] = (uint32_t)c;
-        ord_words += c;
-    }
+    rc = batch_sequences_check(ctx, who, B, G, ascii, seq_off);
+    // a problem run alone costs about kSingleUs per round plus kTailUs for its tail, a lane kLaneUs
+    // per seed-mer of all the rounds (measured: DESIGN.md §5l)
+    constexpr double kLaneUs = 18.0, kSingleUs = 915.0, kTailUs = 380.0;
+    if (!rc) rc = batch_plan(ctx, who, run, {kLaneUs, kSingleUs * (double)rounds + kTailUs});
+    if (rc) return rc;
 
     // starts as MemHash::Clear does; the context's own seed pattern stays as it is
     rc = mums_clear(ctx);
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    ctx->batch_off.assign((size_t)B + 1, 0);
-    ctx->batch_probes.assign(B, 0);
-    ctx->batch_coll.assign(B, 0);
-    ctx->batch_restarts.assign(B, 0);
-    ctx->anchor_table.assign(B, 0);
-    uint64_t Nstat = 0;
-    for (const Round& x : rd) Nstat += x.Nall;
-    if (B == 0) return anchor_done(ctx, G, 0, 0, 0);
+    batch_vectors(ctx, B, true);
+    if (B == 0) return batch_done(ctx, G, 0, true);
 
-    hipStream_t st = ctx->stream;
-    (void)hipEventRecord(ctx->ev[EV_START], st);
-    // per-problem device words: cnt, probes, coll, flag (B each), pool cursor, first '-' offset
-    HIPCHK(ctx->bt_per.ensure(((size_t)4 * B + 4) * 4 + 64));
-    uint32_t* d_cnt = ctx->bt_per.as<uint32_t>();
-    uint32_t *d_probes = d_cnt + B, *d_coll = d_cnt + 2 * (size_t)B, *d_flag = d_cnt + 3 * (size_t)B;
-    uint32_t* d_pool_n = d_cnt + 4 * (size_t)B;
-    unsigned long long* d_first = (unsigned long long*)(d_pool_n + 2);
-    HIPCHK(hipMemsetAsync(ctx->bt_per.p, 0, ((size_t)4 * B + 2) * 4, st));
-    HIPCHK(hipMemsetAsync(d_first, 0xFF, 8, st));
-    HIPCHK(ctx->bt_ascii.ensure(A + 64));
-    if (A) HIPCHK(hipMemcpyAsync(ctx->bt_ascii.p, ascii + a0, A, hipMemcpyHostToDevice, st));
-    // segment tables: aoff, nlen (nseg + 1 u64 each), mbase (nseg + 1 u32), order, obase, ocap (B u32 each)
-    HIPCHK(ctx->bt_seg.ensure(2 * (nseg + 1) * 8 + (nseg + 1 + 3 * (size_t)B) * 4 + 64));
-    uint64_t* d_aoff = ctx->bt_seg.as<uint64_t>();
-    uint64_t* d_nlen = d_aoff + nseg + 1;
-    uint32_t* d_mbase = (uint32_t*)(d_nlen + nseg + 1);
-    uint32_t* d_order = d_mbase + nseg + 1;
-    uint32_t *d_obase = d_order + B, *d_ocap = d_obase + B;
-    HIPCHK(hipMemcpyAsync(d_aoff, aoff.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_nlen, nlen.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_order, order.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_obase, obase.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_ocap, ocap.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(launch_batch_gap(ctx->bt_ascii.as<char>(), 0, A, d_first, st));
-    unsigned long long first_gap = ~0ull;
-    HIPCHK(hipMemcpyAsync(&first_gap, d_first, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (first_gap != ~0ull) {   // SortedMerList.cpp:433-437 throws for the sequence holding it
-        const uint64_t at = a0 + first_gap;
-        const uint64_t s = (uint64_t)(std::upper_bound(seq_off, seq_off + nseg + 1, at) - seq_off) - 1;
-        (void)mums_clear(ctx);
-        return fail(ctx, MUMS_E_GAP, "Gap in genome sequence: problem " + std::to_string(s / G) + " of the batch");
-    }
-
-    double ms_keys = 0, ms_sort = 0, ms_replay = 0;
-    std::vector<uint32_t> per((size_t)4 * B, 0);
-    if (Nmax > 0) {
-        const uint64_t pool_cap64 = std::min<uint64_t>(Nsum / 2 + 1, std::max<uint64_t>(Nsum / 8, 1ull << 16));
-        HIPCHK(ctx->bt_keys.ensure(Nmax * 8 + 64));
-        HIPCHK(ctx->bt_kA.ensure(Nmax * 8 + 64));
-        HIPCHK(ctx->bt_kB.ensure(Nmax * 8 + 64));
-        HIPCHK(ctx->bt_vA.ensure(Nmax * 4 + 64));
-        HIPCHK(ctx->bt_vB.ensure(Nmax * 4 + 64));
-        HIPCHK(ctx->bt_tmp.ensure(radix_tmp_bytes(Nmax) + 256));
-        HIPCHK(ctx->bt_ord.ensure((ord_words + 2) * 8));
-        HIPCHK(ctx->bt_pool.ensure(pool_cap64 * (size_t)(G + 2) * 8 + 64));
-        for (uint32_t r = 0; r < rounds; ++r) {
-            const Round& x = rd[r];
-            if (r > 0) (void)hipEventRecord(ctx->ev[EV_GROUPS], st);   // the round's start
-            if (x.N > 0) {
-                HIPCHK(hipMemcpyAsync(d_mbase, x.mbase.data(), (nseg + 1) * 4, hipMemcpyHostToDevice, st));
-                HIPCHK(launch_batch_keys(ctx->bt_ascii.as<char>(), d_aoff, d_mbase, (uint32_t)nseg, G, (uint32_t)x.N, x.ss,
-                                         x.kbits, ctx->bt_keys.as<uint64_t>(), st));
-            }
-            (void)hipEventRecord(ctx->ev[EV_KEYS], st);
-            int ob = 0;
-            if (x.N > 0)
-                HIPCHK(radix_sort<uint64_t>(ctx->bt_keys.as<uint64_t>(), nullptr, x.N, x.kbits + pbits,
-                                            ctx->bt_kA.as<uint64_t>(), ctx->bt_vA.as<uint32_t>(), ctx->bt_kB.as<uint64_t>(),
-                                            ctx->bt_vB.as<uint32_t>(), ctx->bt_tmp.p, &ob, st));
-            (void)hipEventRecord(ctx->ev[EV_SORT], st);
-            if (x.N > 0) {
-                BatchReplay br{};
-                br.sk = ob == 0 ? ctx->bt_kA.as<uint64_t>() : ctx->bt_kB.as<uint64_t>();
-                br.sv = ob == 0 ? ctx->bt_vA.as<uint32_t>() : ctx->bt_vB.as<uint32_t>();
-                br.keys = ctx->bt_keys.as<uint64_t>();
-                br.mbase = d_mbase;
-                br.nlen = d_nlen;
-                br.order = d_order;
-                br.ord = ctx->bt_ord.as<uint64_t>();
-                br.pool = ctx->bt_pool.as<int64_t>();
-                br.pool_cap = (uint32_t)pool_cap64;
-                br.pool_n = d_pool_n;
-                br.cnt = d_cnt;
-                br.probes = d_probes;
-                br.coll = d_coll;
-                br.flag = d_flag;
-                br.B = B;
-                br.G = G;
-                br.L = x.L;
-                br.kbits = x.kbits;
-                br.table_size = ctx->table_size;
-                br.masked = ctx->masked;
-                br.seq_mask = ctx->seq_mask;
-                br.ord_base = d_obase;
-                br.ord_cap = d_ocap;
-                HIPCHK(launch_batch_replay(br, st));
-            }
-            (void)hipEventRecord(ctx->ev[EV_REPLAY], st);
-            HIPCHK(hipStreamSynchronize(st));   // the next round's mbase replaces this one's; the phase times
-            ms_keys += anchor_ms(ctx, r > 0 ? EV_GROUPS : EV_START, EV_KEYS);
-            ms_sort += anchor_ms(ctx, EV_KEYS, EV_SORT);
-            ms_replay += anchor_ms(ctx, EV_SORT, EV_REPLAY);
-        }
-        HIPCHK(hipMemcpyAsync(per.data(), d_cnt, (size_t)4 * B * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    } else {
-        (void)hipEventRecord(ctx->ev[EV_REPLAY], st);
-        HIPCHK(hipStreamSynchronize(st));
-        ms_keys = anchor_ms(ctx, EV_START, EV_REPLAY);
-    }
-    const uint32_t *h_cnt = per.data(), *h_probes = h_cnt + B, *h_coll = h_cnt + 2 * (size_t)B, *h_flag = h_cnt + 3 * (size_t)B;
-
-    // the problems left out (above the cap, the size rule) or not finished in some round
-    // (MER_REPEAT_LIMIT, pool) run alone, from round 0
-    std::vector<uint64_t> rlen, rcount(B, 0), rfirst(B, 0);
-    std::vector<int64_t> rs;
+    rc = batch_setup(ctx, run);
+    if (rc) return rc;
+    // a problem's table is its slice of ord (the plan's obase / ocap); the entry pool, on the rounds' sum
+    const uint64_t Nsum = run.pl.Nsum;
+    const uint64_t pool_cap64 = std::min<uint64_t>(Nsum / 2 + 1, std::max<uint64_t>(Nsum / 8, 1ull << 16));
+    rc = batch_rounds(ctx, run, run.pl.ord_words + 2, pool_cap64);
+    if (rc) return rc;
+    AloneJob job{G};
+    job.ascii = ascii;
+    job.patterns = patterns;
+    job.rounds = rounds;
+    job.anchor = true;
+    job.eliminate_both = eliminate_both;
+    job.min_length = min_length;
+    BatchAlone al;
+    rc = batch_fallbacks(ctx, who, run, job, al);
+    if (rc) return batch_abort(ctx, rc);
+    // the tail of the lanes' tables, gathered bucket-major into the work arrays
     std::vector<uint64_t> toff((size_t)B + 1, 0);
-    for (uint32_t p = 0; p < B; ++p) {
-        toff[p + 1] = toff[p];
-        if (!routed[p] && !h_flag[p]) {
-            ctx->batch_probes[p] = h_probes[p];
-            ctx->batch_coll[p] = h_coll[p];
-            ctx->anchor_table[p] = h_cnt[p];
-            toff[p + 1] += h_cnt[p];
-            continue;
-        }
-        routed[p] = 1;
-        rfirst[p] = rlen.size();
-        rc = anchor_single(ctx, G, ascii, seq_off + (uint64_t)p * G, patterns, rounds, eliminate_both, min_length, rlen,
-                           rs, &rcount[p], &ctx->anchor_table[p], &ctx->batch_probes[p], &ctx->batch_coll[p],
-                           &ctx->batch_restarts[p]);
-        if (rc) {
-            const std::string msg = ctx->err;
-            (void)mums_clear(ctx);
-            return fail(ctx, rc, msg);
-        }
-    }
-    HIPCHK(hipSetDevice(ctx->device));
+    for (uint32_t p = 0; p < B; ++p) toff[p + 1] = toff[p] + (al.routed[p] ? 0 : run.per[p]);
     auto fill = [&](uint64_t* d_toff, int64_t* d_wlen, int64_t* d_ws) -> hipError_t {
         if (toff[B] == 0) return hipSuccess;
-        return launch_anchor_gather(ctx->bt_ord.as<uint64_t>(), d_obase, ctx->bt_pool.as<int64_t>(), d_toff, B, G, d_wlen,
-                                    d_ws, st);
+        return launch_anchor_gather(ctx->bt_ord.as<uint64_t>(), run.d_obase, ctx->bt_pool.as<int64_t>(), d_toff, B, G, d_wlen,
+                                    d_ws, ctx->stream);
     };
-    uint64_t M = 0;
-    rc = anchor_tail_stage(ctx, who, B, G, toff, routed, rlen, rs, rcount, rfirst, eliminate_both, min_length, fill, &M);
-    if (rc) {
-        const std::string msg = ctx->err;
-        (void)mums_clear(ctx);
-        return fail(ctx, rc, msg);
-    }
-    uint64_t P = 0, C = 0, R = 0, E = 0;
-    for (uint32_t p = 0; p < B; ++p) {
-        P += ctx->batch_probes[p];
-        C += ctx->batch_coll[p];
-        R += ctx->batch_restarts[p];
-        E += ctx->anchor_table[p];
-    }
-    mums_stats& s = ctx->st;
-    s = mums_stats{};
-    s.seedmers = Nstat;
-    s.probes = P;
-    s.mem_count = E;
-    s.collision_count = C;
-    s.restarts = R;
-    s.repeat_limit_groups = R;
-    s.key_bytes = 8;
-    for (const Round& x : rd) s.sort_passes += (uint64_t)((x.kbits + pbits + 7) / 8);
-    s.ms_keys = ms_keys;
-    s.ms_sort = ms_sort;
-    s.ms_replay = ms_replay;
-    s.ms_output = anchor_ms(ctx, EV_REPLAY, EV_OUTPUT);
-    s.ms_total = anchor_ms(ctx, EV_START, EV_OUTPUT);
-    return anchor_done(ctx, G, M, P, Nstat);
+    uint64_t M = 0, E = 0;
+    rc = anchor_tail_stage(ctx, who, B, G, toff, al, eliminate_both, min_length, fill, &M);
+    if (rc) return batch_abort(ctx, rc);
+    for (uint32_t p = 0; p < B; ++p) E += ctx->anchor_table[p];
+    batch_stats(ctx, run, E);
+    return batch_done(ctx, G, M, true);
 }
 
 int mums_anchor_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* table_entries, uint64_t* probes,
@@ -4050,11 +3838,7 @@ int mums_anchor_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* table_e
     if (check_ctx(ctx)) return MUMS_E_INVALID;
     if (!ctx->batch_result || !ctx->anchor_result)
         return fail(ctx, MUMS_E_INVALID, "no completed mums_anchor_batch / mums_anchor_tail_batch on this context");
-    if (match_off) std::copy(ctx->batch_off.begin(), ctx->batch_off.end(), match_off);
-    if (table_entries) std::copy(ctx->anchor_table.begin(), ctx->anchor_table.end(), table_entries);
-    if (probes) std::copy(ctx->batch_probes.begin(), ctx->batch_probes.end(), probes);
-    if (collisions) std::copy(ctx->batch_coll.begin(), ctx->batch_coll.end(), collisions);
-    if (restarts) std::copy(ctx->batch_restarts.begin(), ctx->batch_restarts.end(), restarts);
+    batch_info(ctx, match_off, table_entries, probes, collisions, restarts);
     return MUMS_OK;
 }
 

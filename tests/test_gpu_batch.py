@@ -332,3 +332,59 @@ def test_gap_names_the_problem(gpu_lib, oracle_mod):
             mh.FindMatchesBatch(bad, [seed] * 5)
         assert "problem 3" in str(e.value)
         check_batch(gpu_lib, oracle_mod, problems, seed, mh=mh)
+
+
+def _mixed_routings(rng):
+    """A lane problem, one above the MUMS_DEV_BATCH_CAP the test sets, and test_mer_repeat_limit_problems'
+    poly-A problem, which a lane gives up (below that cap: 4600 seed-mers)."""
+    a, b = pair(rng, 800)
+    return [pair(rng, 1000), pair(rng, 3500), (a[:400] + b"A" * 1500 + a[400:], b[:300] + b"A" * 1500 + b[300:])]
+
+
+@pytest.mark.parametrize("batch", ["g3", "mixed"])
+def test_find_batch_and_one_round_anchor_batch_agree(gpu_lib, oracle_mod, batch):
+    """mums_find_batch and mums_anchor_batch share one host engine: with one round and min_length 0
+    the anchor call's table is the find call's list.  Per problem and in mums_get_stats the two agree,
+    every find list is the oracle's, and the anchor call's final lists are mums_anchor_tail_batch of
+    the find lists: one MemHash, both routings of the size rule."""
+    import anchor_batch_cases as ab
+    if batch == "g3":
+        case = ab.find_case("g3")
+        problems, seed, cap = case["problems"], case["patterns"][0][0], None
+    else:
+        problems, seed, cap = _mixed_routings(np.random.default_rng(114)), oracle_mod.get_seed(9), "6000"
+    B = len(problems)
+    refs = [oracle_mod.find_matches(list(prob), seed, table_size=40000) for prob in problems]
+    if batch == "mixed":
+        assert [r[2]["restarts"] for r in refs] == [0, 0, 1]
+    one_round = dict(problems=problems, patterns=[(seed,)] * B)
+    totals = ("seedmers", "probes", "collision_count", "restarts", "sort_passes", "key_bytes")
+    with gpu_lib.MemHash(0) as mh:
+        mh.SetTableSize(40000)
+        try:
+            if cap:
+                os.environ["MUMS_DEV_BATCH_CAP"] = cap
+            for no_split in ("1", None):
+                if no_split:
+                    os.environ["MUMS_DEV_BATCH_NO_SPLIT"] = no_split
+                else:
+                    os.environ.pop("MUMS_DEV_BATCH_NO_SPLIT", None)
+                found = mh.FindMatchesBatch(problems, [seed] * B)
+                f_info, f_st = mh.BatchInfo(), mh.stats()
+                anchored, a_info = ab.run_find_case(mh, one_round, False, min_length=0)
+                a_st = mh.stats()
+                tails = mh.AnchorTailBatch(found, eliminate_both=False, min_length=0)
+                for p, (rl, rs, st) in enumerate(refs):
+                    assert np.array_equal(found[p].lengths, rl) and np.array_equal(found[p].starts, rs), p
+                    assert int(f_info["probes"][p]) == int(a_info["probes"][p]) == st["probes"], p
+                    assert int(f_info["collisions"][p]) == int(a_info["collisions"][p]) == st["collision_count"], p
+                    assert int(f_info["restarts"][p]) == int(a_info["restarts"][p]) == st["restarts"], p
+                    assert int(f_info["matches"][p]) == int(a_info["table_entries"][p]) == len(rl), p
+                    assert np.array_equal(anchored[p].lengths, tails[p].lengths), p
+                    assert np.array_equal(anchored[p].starts, tails[p].starts), p
+                for k in totals:
+                    assert f_st[k] == a_st[k], (k, f_st[k], a_st[k])
+                assert f_st["probes"] == sum(r[2]["probes"] for r in refs) and f_st["key_bytes"] == 8
+        finally:
+            os.environ.pop("MUMS_DEV_BATCH_CAP", None)
+            os.environ.pop("MUMS_DEV_BATCH_NO_SPLIT", None)
