@@ -333,6 +333,29 @@ int  mums_anchor_tail_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const uint64_
  * MUMS_E_INVALID when the context holds no such result. */
 int  mums_anchor_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* table_entries, uint64_t* probes,
                             uint64_t* collisions, uint64_t* restarts);
+/* The gap search of Aligner::Recursion (Aligner.cpp:1136-1218, mauveAligner) for B problems in one
+ * call.  Sequences, patterns[rounds] (1 to 8 rounds, every pattern != 0, any order), table size,
+ * mask, limits, refusals and the problems run alone inside the call: all as in mums_anchor_batch.
+ * Per problem: Clear; per round ClearSequences + FindMatches(patterns[r]) on all G sequences into
+ * one table (:1142-1203; which rounds a problem has is the caller's choice, the default weights of
+ * its sequences decide it there); the table in GetMatchList order through EliminateOverlaps (the v1
+ * of Aligner.cpp:62-176, which appends the cut-off overlap of a pair as a new match);
+ * MultiplicityFilter(multiplicity) (MatchList.h:636-649: keeps Multiplicity() == multiplicity; 0: no
+ * filter; nway_only passes G); LengthFilter(min_length) (MIN_ANCHOR_LENGTH = 9 there; 0 keeps
+ * everything).  Problem p's part of the result is bit for bit, order included, what mums_clear; per
+ * round mums_clear_sequences, mums_set_seed, the sequences, mums_find; mums_eliminate_overlaps;
+ * mums_multiplicity_filter; mums_length_filter give for p alone.
+ * Result and state afterwards as after mums_anchor_batch; mums_anchor_batch_info and
+ * mums_batch_info answer for it (table_entries = MemCount before the tail), mums_get_stats is
+ * filled as there.  A list that outgrows its share of the work arrays, or has more than 1024 rows,
+ * runs through the single-problem calls inside the call (the same result). */
+int  mums_recursion_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const char* ascii, const uint64_t* seq_off,
+                          const uint64_t* patterns, uint32_t rounds, uint32_t multiplicity, uint64_t min_length);
+/* The same tail on the caller's lists; arguments and checks as in mums_anchor_tail_batch
+ * (table_entries = the input row counts). */
+int  mums_recursion_tail_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const uint64_t* match_off,
+                               const uint64_t* lengths, const int64_t* starts, uint32_t multiplicity,
+                               uint64_t min_length);
 /* Test entry point: ids[0..n) = the permutation libstdc++ std::sort leaves on keys with
  * operator< (depth_override >= 0 forces the introsort depth limit; -1 = 2*lg(n)). */
 int  mums_debug_std_sort(mums_ctx* ctx, const uint64_t* keys, uint64_t n, int depth_override, uint32_t* ids);

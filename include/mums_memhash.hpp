@@ -12,6 +12,7 @@
 
 #include <array>
 #include <cstdint>
+#include <map>
 #include <memory>
 #include <ostream>
 #include <stdexcept>
@@ -358,6 +359,103 @@ public:
         batch_collect(idx, out, true);
     }
     const AnchorCounters& AnchorBatchInfo() const { return anchor_; }
+    // The seed weights Aligner::Recursion searches one gap problem with, in its order (descending):
+    // Aligner.cpp:1142-1203 restated literally.  weights: the seed weights of the G gap sequences
+    // (getDefaultSeedWeight of their lengths, :1145).  nway_only skips a stop that has not collected
+    // every sequence yet (:1192).  Every search is on all G sequences.
+    static std::vector<uint32_t> recursion_rounds(const std::vector<uint32_t>& weights, bool nway_only) {
+        const uint32_t kMinDnaSeedWeight = 5;   // SeedMasks.h:375
+        std::multimap<uint32_t, uint32_t> mer_sizes;
+        for (uint32_t seqI = 0; seqI < weights.size(); ++seqI) mer_sizes.insert({weights[seqI], seqI});
+        std::vector<uint32_t> out;
+        if (mer_sizes.empty()) return out;
+        auto mer_iter = mer_sizes.end();
+        mer_iter--;
+        std::vector<uint32_t> search_seqs;
+        while (mer_iter != mer_sizes.end()) {
+            uint32_t prev_mer = mer_iter->first;
+            while (true) {
+                if (mer_iter->first < kMinDnaSeedWeight) break;
+                if (mer_iter->first == prev_mer || search_seqs.size() < 2) {
+                    search_seqs.push_back(mer_iter->second);
+                    if (mer_iter == mer_sizes.begin()) {
+                        mer_iter = mer_sizes.end();   // signify that the scan is complete
+                        break;
+                    }
+                    prev_mer = mer_iter->first;
+                    mer_iter--;
+                } else
+                    break;
+            }
+            if (search_seqs.size() < 2) break;
+            if (prev_mer < kMinDnaSeedWeight) break;
+            if (nway_only && search_seqs.size() < weights.size()) continue;
+            out.push_back(prev_mer);
+        }
+        return out;
+    }
+    // The gap search of Aligner::Recursion (Aligner.cpp:1136-1218) for many gap problems in one device
+    // pass per list of rounds (mums_recursion_batch): per problem Clear; per weight of
+    // recursion_rounds ClearSequences + FindMatches on all G sequences into one table;
+    // EliminateOverlaps (v1); MultiplicityFilter(G) when nway_only; LengthFilter(min_length).
+    // weights empty: getDefaultSeedWeight(length) per sequence; else per problem its G weights.  A
+    // problem without a round gets an empty list and no search.  AnchorBatchInfo() has the counters.
+    virtual void RecursionBatch(const std::vector<std::vector<std::string>>& problems, std::vector<MatchList>& out,
+                                bool nway_only = false, uint64_t min_length = 9,
+                                const std::vector<std::vector<uint32_t>>& weights = {}) {
+        const size_t B = problems.size(), G = B ? problems[0].size() : 2;
+        if (!weights.empty() && weights.size() != B) throw InvalidData("RecursionBatch: one list of seed weights per problem");
+        batch_begin(B, out, true);
+        std::vector<std::vector<uint64_t>> keys;
+        std::vector<std::vector<size_t>> members;
+        for (size_t p = 0; p < B; ++p) {
+            if (problems[p].size() != G) throw InvalidData("RecursionBatch: every problem needs the same sequence count");
+            std::vector<uint32_t> ws;
+            if (!weights.empty()) ws = weights[p];
+            else
+                for (const std::string& s : problems[p]) ws.push_back(mums_default_seed_weight(s.size()));
+            if (ws.size() != G) throw InvalidData("RecursionBatch: one seed weight per sequence");
+            std::vector<uint64_t> pats;
+            for (uint32_t w : recursion_rounds(ws, nway_only)) pats.push_back((uint64_t)mums_get_seed((int)w, 0));
+            if (pats.empty()) continue;
+            size_t k = 0;
+            while (k < keys.size() && keys[k] != pats) ++k;
+            if (k == keys.size()) { keys.push_back(pats); members.emplace_back(); }
+            members[k].push_back(p);
+        }
+        if (keys.empty()) check(mums_clear(ctx_));
+        for (size_t k = 0; k < keys.size(); ++k) {
+            std::string blob;
+            std::vector<uint64_t> off;
+            batch_blob(problems, members[k], blob, off);
+            check(mums_recursion_batch(ctx_, (uint32_t)members[k].size(), (uint32_t)G, blob.data(), off.data(), keys[k].data(),
+                                       (uint32_t)keys[k].size(), nway_only ? (uint32_t)G : 0, min_length));
+            batch_collect(members[k], out, true);
+        }
+    }
+    // Aligner::Recursion's tail on the caller's lists in one device pass (mums_recursion_tail_batch):
+    // EliminateOverlaps (v1), MultiplicityFilter(multiplicity) (0: none), LengthFilter(min_length),
+    // each list on its own; seq_count sequences per match in every list.
+    virtual void RecursionTailBatch(const std::vector<MatchList>& lists, uint32_t seq_count, std::vector<MatchList>& out,
+                                    uint32_t multiplicity = 0, uint64_t min_length = 9) {
+        const size_t B = lists.size();
+        std::vector<uint64_t> off(1, 0), len;
+        std::vector<int64_t> st;
+        for (const MatchList& ml : lists) {
+            for (const Match& m : ml) {
+                if (m.starts.size() != seq_count) throw InvalidData("RecursionTailBatch: a match with another sequence count");
+                len.push_back(m.length);
+                st.insert(st.end(), m.starts.begin(), m.starts.end());
+            }
+            off.push_back(len.size());
+        }
+        check(mums_recursion_tail_batch(ctx_, (uint32_t)B, seq_count, off.data(), len.data(), st.data(), multiplicity,
+                                        min_length));
+        batch_begin(B, out, true);
+        std::vector<size_t> idx(B);
+        for (size_t p = 0; p < B; ++p) idx[p] = p;
+        batch_collect(idx, out, true);
+    }
     // MemHash::CreateMatches (MemHash.cpp:104-107)
     virtual bool CreateMatches() {
         check(mums_find(ctx_));

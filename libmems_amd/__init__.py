@@ -112,6 +112,7 @@ EXPORTED_SYMBOLS = [
     "mums_shard_chain_info", "mums_shard_chain_entries", "mums_shard_entry_thresholds", "mums_shard_kept_export",
     "mums_shard_find_kept", "mums_comm_exchange_info", "mums_eliminate_overlaps_v2", "mums_clear_sequences",
     "mums_find_batch", "mums_batch_info", "mums_anchor_batch", "mums_anchor_tail_batch", "mums_anchor_batch_info",
+    "mums_recursion_batch", "mums_recursion_tail_batch",
 ]
 
 # mums_comm_ops (include/mums.h): the caller's transport as two host callbacks
@@ -241,6 +242,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mums_anchor_batch.argtypes = [vp, u32, u32, vp, vp, vp, u32, i32, u64]
     lib.mums_anchor_tail_batch.argtypes = [vp, u32, u32, vp, vp, vp, i32, u64]
     lib.mums_anchor_batch_info.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.mums_recursion_batch.argtypes = [vp, u32, u32, vp, vp, vp, u32, u32, u64]
+    lib.mums_recursion_tail_batch.argtypes = [vp, u32, u32, vp, vp, vp, u32, u64]
     _lib = lib
     return lib
 
@@ -317,6 +320,76 @@ def anchor_seed_groups(problems: Sequence[Sequence[bytes]], seed_families: bool 
     ranks = (0, 1, 2) if seed_families else (0,)
     patterns = {w: [get_seed(w, r) for r in ranks] for w in groups}
     return ws, groups, patterns
+
+
+MIN_DNA_SEED_WEIGHT = 5   # SeedMasks.h: below it getSeed has no pattern
+
+
+def recursion_rounds(lengths: Sequence[int], nway_only: bool = False, weights: Optional[Sequence[int]] = None,
+                     default_weight=None) -> List[int]:
+    """The seed weights Aligner::Recursion searches one gap problem with, in its order (descending):
+    Aligner.cpp:1142-1203 restated literally, host logic only.  lengths: the G gap sequences'
+    lengths; weights: their seed weights when not getDefaultSeedWeight(length) (:1145).  The loop
+    walks the sequences by descending weight, collects those of one weight (and the next ones while
+    fewer than two are collected), stops at a weight below MIN_DNA_SEED_WEIGHT and searches once per
+    stop with the last collected weight; nway_only skips a stop that has not collected every
+    sequence yet (:1192, no ClearSequences either).  Every search is on all G sequences."""
+    default_weight = default_weight or getDefaultSeedWeight
+    ws = [int(w) for w in weights] if weights is not None else [int(default_weight(int(n))) for n in lengths]
+    seq_count = len(ws)
+    if seq_count == 0:
+        return []
+    mer_sizes = sorted((w, i) for i, w in enumerate(ws))   # multimap< uint, uint >: ascending by weight
+    end = -1                                               # mer_sizes.end()
+    it = len(mer_sizes) - 1                                # mer_iter = end(); mer_iter--
+    search_seqs: List[int] = []
+    out: List[int] = []
+    while it != end:
+        prev_mer = mer_sizes[it][0]
+        while True:
+            if mer_sizes[it][0] < MIN_DNA_SEED_WEIGHT:
+                break
+            if mer_sizes[it][0] == prev_mer or len(search_seqs) < 2:
+                search_seqs.append(mer_sizes[it][1])
+                if it == 0:        # mer_iter == mer_sizes.begin()
+                    it = end       # signify that the scan is complete
+                    break
+                prev_mer = mer_sizes[it][0]
+                it -= 1
+            else:
+                break
+        if len(search_seqs) < 2:
+            break
+        if prev_mer < MIN_DNA_SEED_WEIGHT:
+            break
+        if nway_only and len(search_seqs) < seq_count:
+            continue   # no sense in searching for matches in subsets
+        out.append(prev_mer)
+    return out
+
+
+def recursion_groups(problems: Sequence[Sequence[bytes]], nway_only: bool = False, weights=None, default_weight=None,
+                     get_seed=None):
+    """The grouping of MemHash.RecursionBatch, host logic only: (patterns, groups).  patterns[p] =
+    the tuple getSeed(w, 0) for w in recursion_rounds(problem p); groups = {tuple: [problem indices
+    in order]} for the non-empty tuples in order of first appearance.  weights: per problem the G
+    seed weights of its sequences."""
+    get_seed = get_seed or getSeed
+    if weights is not None and len(weights) != len(problems):
+        raise ValueError("RecursionBatch: one list of seed weights per problem")
+    patterns: List[tuple] = []
+    groups: dict = {}
+    seeds: dict = {}
+    for p, prob in enumerate(problems):
+        ws = recursion_rounds([len(s) for s in prob], nway_only, None if weights is None else weights[p], default_weight)
+        for w in ws:
+            if w not in seeds:
+                seeds[w] = int(get_seed(w, 0))
+        pats = tuple(seeds[w] for w in ws)
+        patterns.append(pats)
+        if pats:
+            groups.setdefault(pats, []).append(p)
+    return patterns, groups
 
 
 # the per-problem counters of BatchInfo() / AnchorBatchInfo(), after "matches" in the order of the C calls
@@ -585,6 +658,62 @@ class MemHash:
         self._batch_collect(list(range(B)), G, out, info)
         self._anchor_info = info
         return out  # type: ignore[return-value]
+
+    def RecursionBatch(self, problems: Sequence[Sequence[bytes]], nway_only: bool = False, min_length: int = 9,
+                       weights=None) -> List[MatchList]:
+        """The gap search of Aligner::Recursion (Aligner.cpp:1136-1218) for many gap problems in one
+        device pass per list of rounds (mums_recursion_batch): per problem Clear; per seed weight of
+        recursion_rounds(its lengths, nway_only) ClearSequences + FindMatches on all G sequences
+        into one table; EliminateOverlaps (v1); MultiplicityFilter(G) when nway_only;
+        LengthFilter(min_length) (MIN_ANCHOR_LENGTH = 9).  problems: G-tuples of bytes, the same G
+        for all; weights: per problem its sequences' seed weights instead of the defaults.  A
+        problem without a round gets an empty list and no device work.  The below_cutoff_count gate
+        (:1136) is the caller's.  Returns one MatchList per problem with starts in the problem's own
+        sequences; RecursionBatchInfo() has every problem's counters."""
+        problems, G, out, info = self._batch_begin("RecursionBatch", problems, _ANCHOR_KEYS)
+        patterns, groups = recursion_groups(problems, nway_only, weights)
+        self._batch_skip([p for p, pats in enumerate(patterns) if not pats], G, out, groups)
+        for pats, idx in groups.items():
+            blob, off = _batch_blob(problems, idx)
+            pa = np.asarray(pats, dtype=np.uint64)
+            self._check(self._lib.mums_recursion_batch(self._ctx, len(idx), G, blob, off.ctypes.data, pa.ctypes.data,
+                                                       len(pa), G if nway_only else 0, int(min_length)))
+            self._batch_collect(idx, G, out, info)
+        self._recursion_info = info
+        return out  # type: ignore[return-value]
+
+    def RecursionTailBatch(self, lists: Sequence["MatchList"], multiplicity: int = 0, min_length: int = 9) -> List[MatchList]:
+        """Aligner::Recursion's tail on the caller's lists in one device pass
+        (mums_recursion_tail_batch): EliminateOverlaps (v1), MultiplicityFilter(multiplicity) (0:
+        none), LengthFilter(min_length), each list on its own.  Every list needs the same number of
+        sequences."""
+        B = len(lists)
+        shapes = {int(np.asarray(ml.starts).shape[1]) for ml in lists if np.asarray(ml.starts).ndim == 2}
+        if len(shapes) > 1:
+            raise ValueError("RecursionTailBatch: every list needs the same number of sequences")
+        G = shapes.pop() if shapes else 2
+        rows = [np.ascontiguousarray(ml.starts, dtype=np.int64).reshape(len(ml), G) for ml in lists]
+        lengths = np.ascontiguousarray(np.concatenate([np.asarray(ml.lengths, dtype=np.uint64) for ml in lists])
+                                       if B else np.zeros(0, dtype=np.uint64))
+        starts = np.ascontiguousarray(np.concatenate(rows) if B else np.zeros((0, G), dtype=np.int64))
+        off = np.zeros(B + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(ml) for ml in lists], dtype=np.uint64)
+        self._keepalive.clear()
+        self._check(self._lib.mums_recursion_tail_batch(self._ctx, B, G, off.ctypes.data, lengths.ctypes.data,
+                                                        starts.ctypes.data, int(multiplicity), int(min_length)))
+        out: List[Optional[MatchList]] = [None] * B
+        info = {k: np.zeros(B, dtype=np.uint64) for k in _ANCHOR_KEYS}
+        self._batch_collect(list(range(B)), G, out, info)
+        self._recursion_info = info
+        return out  # type: ignore[return-value]
+
+    def RecursionBatchInfo(self) -> dict:
+        """Per problem of the last RecursionBatch / RecursionTailBatch: matches (final rows),
+        table_entries (MemCount before the tail; the input rows of a tail call), probes, collisions
+        and restarts over all rounds, as uint64 arrays."""
+        if getattr(self, "_recursion_info", None) is None:
+            raise MumsError(MUMS_E_INVALID, "no RecursionBatch on this object")
+        return self._recursion_info
 
     def AnchorBatchInfo(self) -> dict:
         """Per problem of the last AnchorSearchBatch / AnchorTailBatch: matches (final rows),
@@ -1067,4 +1196,5 @@ __all__ = [
     "MemHash", "MaskedMemHash", "ParallelMemHash", "PairwiseMatchFinder", "MatchList", "MumsError", "GapInSequence", "getSeed", "getSeedLength",
     "getSeedWeight", "getDefaultSeedWeight", "load_library", "EXPORTED_SYMBOLS", "STAGE_SEEDS", "STAGE_ALL", "ShardedMemHash",
     "shard_key_ranges", "EliminateOverlaps", "EliminateOverlaps_v2", "batch_seed_groups", "anchor_seed_groups",
+    "recursion_rounds", "recursion_groups",
 ]

@@ -19,13 +19,15 @@ namespace {
 
 constexpr int kAnchorBlock = 64;   // tail: lanes (= problems) per workgroup
 
-// rows [toff[p], toff[p + 1]) of wlen / ws = problem p's table in GetMatchList order (ord slice at obase[p])
+// rows [toff[p], toff[p + 1]) of wlen / ws = problem p's table in GetMatchList order (ord slice at
+// obase[p]); with nrow the table has nrow[p] rows (recursion.hip: a slice wider than its input)
 __global__ void anchor_gather_kernel(const uint64_t* __restrict__ ord, const uint32_t* __restrict__ obase,
                                      const int64_t* __restrict__ pool, const uint64_t* __restrict__ toff, uint32_t G,
-                                     int64_t* __restrict__ wlen, int64_t* __restrict__ ws) {
+                                     int64_t* __restrict__ wlen, int64_t* __restrict__ ws,
+                                     const uint32_t* __restrict__ nrow) {
     const uint32_t p = blockIdx.x;
     const uint64_t d = toff[p];
-    const uint32_t n = (uint32_t)(toff[p + 1] - d);
+    const uint32_t n = nrow ? nrow[p] : (uint32_t)(toff[p + 1] - d);
     const uint64_t* o = ord + obase[p];
     for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) {
         const int64_t* row = pool + (uint64_t)(uint32_t)o[k] * (uint64_t)(G + 2);
@@ -66,9 +68,10 @@ __global__ void anchor_emit_kernel(const uint32_t* __restrict__ V, const int64_t
 }  // namespace
 
 hipError_t launch_anchor_gather(const uint64_t* ord, const uint32_t* obase, const int64_t* pool, const uint64_t* toff,
-                                uint32_t B, uint32_t G, int64_t* wlen, int64_t* ws, hipStream_t st) {
+                                uint32_t B, uint32_t G, int64_t* wlen, int64_t* ws, hipStream_t st,
+                                const uint32_t* nrow) {
     if (B == 0) return hipSuccess;
-    hipLaunchKernelGGL(anchor_gather_kernel, dim3(B), dim3(64), 0, st, ord, obase, pool, toff, G, wlen, ws);
+    hipLaunchKernelGGL(anchor_gather_kernel, dim3(B), dim3(64), 0, st, ord, obase, pool, toff, G, wlen, ws, nrow);
     return hipGetLastError();
 }
 

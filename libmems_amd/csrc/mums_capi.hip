@@ -165,7 +165,8 @@ struct mums_ctx {
     bool batch_result = false;
     std::vector<uint64_t> batch_off, batch_probes, batch_coll, batch_restarts;   // B + 1 / B / B / B
     mums_ctx* batch_sub = nullptr;   // problems the lanes leave out: the single-problem pipeline
-    // mums_anchor_batch / mums_anchor_tail_batch (anchor.hip): a batch result whose lists went through the tail
+    // mums_anchor_batch / mums_anchor_tail_batch (anchor.hip), mums_recursion_batch / mums_recursion_tail_batch
+    // (recursion.hip): a batch result whose lists went through the tail
     bool anchor_result = false;
     std::vector<uint64_t> anchor_table;   // B: entries before the tail
     DevBuf an_K, an_V, an_wlen, an_ws, an_per;
@@ -3222,7 +3223,8 @@ struct BatchRun {
 };
 
 // what runs alone on the sub-context: a problem's sequences through `rounds` finds, or (rounds == 0)
-// a finished list; anchor: ClearSequences before every round, EliminateOverlaps_v2 and LengthFilter after
+// a finished list; anchor: ClearSequences before every round, EliminateOverlaps_v2 and LengthFilter after;
+// recursion: ClearSequences before every round, EliminateOverlaps (v1), MultiplicityFilter, LengthFilter after
 struct AloneJob {
     uint32_t G;
     const char* ascii = nullptr;
@@ -3234,6 +3236,8 @@ struct AloneJob {
     const int64_t* s = nullptr;
     bool anchor = false;
     int eliminate_both = 0;
+    bool recursion = false;
+    uint32_t multiplicity = 0;   // 0: no MultiplicityFilter
     uint64_t min_length = 0;
 };
 
@@ -3453,7 +3457,7 @@ static int batch_alone(mums_ctx* ctx, const std::string& who, const AloneJob& j,
     if (!rc && j.rounds) rc = mums_set_params(sub, 0, 1, ctx->table_size);
     if (!rc && j.rounds) rc = mums_set_mask(sub, ctx->masked, ctx->seq_mask);
     for (uint32_t r = 0; r < j.rounds && !rc; ++r) {
-        if (j.anchor) rc = mums_clear_sequences(sub);
+        if (j.anchor || j.recursion) rc = mums_clear_sequences(sub);
         if (!rc) rc = mums_set_seed(sub, j.patterns[r]);
         for (uint32_t g = 0; g < j.G && !rc; ++g) rc = mums_add_genome(sub, j.ascii + j.so[g], j.so[g + 1] - j.so[g]);
         if (!rc) rc = mums_find(sub);
@@ -3466,7 +3470,9 @@ static int batch_alone(mums_ctx* ctx, const std::string& who, const AloneJob& j,
     if (!rc && j.rounds) rc = mums_result_count(sub, &ctx->anchor_table[p], nullptr);
     if (!rc && !j.rounds) rc = mums_load_matches(sub, j.G, j.n, j.len, j.s);
     if (!rc && j.anchor) rc = mums_eliminate_overlaps_v2(sub, nullptr, 0, j.eliminate_both);
-    if (!rc && j.anchor) rc = mums_length_filter(sub, j.min_length);
+    if (!rc && j.recursion) rc = mums_eliminate_overlaps(sub);
+    if (!rc && j.recursion && j.multiplicity) rc = mums_multiplicity_filter(sub, j.multiplicity);
+    if (!rc && (j.anchor || j.recursion)) rc = mums_length_filter(sub, j.min_length);
     uint64_t M = 0;
     if (!rc) rc = mums_result_count(sub, &M, nullptr);
     al.rfirst[p] = al.rlen.size();
@@ -3840,6 +3846,233 @@ int mums_anchor_batch_info(mums_ctx* ctx, uint64_t* match_off, uint64_t* table_e
         return fail(ctx, MUMS_E_INVALID, "no completed mums_anchor_batch / mums_anchor_tail_batch on this context");
     batch_info(ctx, match_off, table_entries, probes, collisions, restarts);
     return MUMS_OK;
+}
+
+// ---- Aligner::Recursion batched: the same engine, recursion.hip's v1 tail ----
+// The tail of every list and the context's MatchList.  List p has nrow[p] rows; fill() puts them
+// into the first rows of p's slice of the work arrays (d_soff, d_nrow, d_wlen, d_ws) on the
+// context's stream.  A list of al is final already.  A list above kAnchorTailCap runs alone before
+// the lanes, one whose slice a lane finds too small after them: job_of(p) is what runs then.
+using RecursionFill = std::function<hipError_t(const std::vector<uint64_t>& soff, uint64_t*, uint32_t*, int64_t*, int64_t*)>;
+static int recursion_tail_stage(mums_ctx* ctx, const std::string& who, uint32_t B, uint32_t G,
+                                const std::vector<uint64_t>& nrow, BatchAlone& al, uint32_t multiplicity,
+                                uint64_t min_length, const RecursionFill& fill,
+                                const std::function<AloneJob(uint32_t)>& job_of, uint64_t* M_out) {
+    hipStream_t st = ctx->stream;
+    auto alone = [&](uint32_t p) {
+        const AloneJob job = job_of(p);
+        if (job.rounds) ctx->batch_probes[p] = ctx->batch_coll[p] = ctx->batch_restarts[p] = 0;   // the lanes' rounds do not count
+        const int rc = batch_alone(ctx, who, job, al, p);
+        if (rc) return rc;
+        HIPCHK(hipSetDevice(ctx->device));
+        return (int)MUMS_OK;
+    };
+    uint32_t before = 0, above = 0, flagged = 0;   // lists run alone: by the plan or the rounds, above the row cap, slice full
+    for (uint32_t p = 0; p < B; ++p) before += al.routed[p] != 0;
+    for (uint32_t p = 0; p < B; ++p)
+        if (!al.routed[p] && nrow[p] > kAnchorTailCap) {
+            const int rc = alone(p);
+            if (rc) return rc;
+            ++above;
+        }
+    std::vector<uint64_t> soff((size_t)B + 1, 0);
+    std::vector<uint32_t> h_nrow(B, 0);
+    for (uint32_t p = 0; p < B; ++p) {
+        if (!al.routed[p]) h_nrow[p] = (uint32_t)nrow[p];
+        soff[p + 1] = soff[p] + (al.routed[p] ? 0 : recursion_slice_rows(nrow[p], G));
+    }
+    const uint64_t S = soff[B];
+    if (S >= 0xFFFFFFF0ull) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": the lists' slices need 2^32 rows or more (split the batch)");
+    // soff (B + 1 u64), doff (B u64), cnt, flag, nrow, order (B u32 each), skip (B bytes)
+    HIPCHK(ctx->an_per.ensure(((size_t)2 * B + 1) * 8 + (size_t)4 * B * 4 + B + 64));
+    uint64_t* d_soff = ctx->an_per.as<uint64_t>();
+    uint64_t* d_doff = d_soff + B + 1;
+    uint32_t* d_cnt = (uint32_t*)(d_doff + B);
+    uint32_t* d_flag = d_cnt + B;
+    uint32_t* d_nrow = d_flag + B;
+    uint32_t* d_order = d_nrow + B;
+    uint8_t* d_skip = (uint8_t*)(d_order + B);
+    HIPCHK(ctx->an_wlen.ensure((S + 1) * 8));
+    HIPCHK(ctx->an_ws.ensure((S + 1) * (size_t)G * 8 + 8));
+    HIPCHK(ctx->an_K.ensure((S + 1) * 8));
+    HIPCHK(ctx->an_V.ensure((S + 1) * 4 + 8));
+    HIPCHK(hipMemcpyAsync(d_soff, soff.data(), ((size_t)B + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_nrow, h_nrow.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    {
+        const hipError_t e = fill(soff, d_soff, d_nrow, ctx->an_wlen.as<int64_t>(), ctx->an_ws.as<int64_t>());
+        if (e != hipSuccess) return fail(ctx, MUMS_E_HIP, who + ": " + hipGetErrorString(e));
+    }
+    const std::vector<uint8_t> skip = al.routed;
+    std::vector<uint32_t> order(B);
+    for (uint32_t p = 0; p < B; ++p) order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return h_nrow[x] > h_nrow[y]; });
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_skip, skip.data(), (size_t)B, hipMemcpyHostToDevice, st));
+    RecursionTail rt{};
+    rt.K = ctx->an_K.as<uint64_t>();
+    rt.V = ctx->an_V.as<uint32_t>();
+    rt.wlen = ctx->an_wlen.as<int64_t>();
+    rt.ws = ctx->an_ws.as<int64_t>();
+    rt.soff = d_soff;
+    rt.nrow = d_nrow;
+    rt.order = d_order;
+    rt.skip = d_skip;
+    rt.cnt = d_cnt;
+    rt.flag = d_flag;
+    rt.B = B;
+    rt.G = G;
+    rt.multiplicity = multiplicity;
+    rt.min_length = min_length;
+    HIPCHK(launch_recursion_tail(rt, st));
+    std::vector<uint32_t> h_cnt((size_t)2 * B, 0);   // cnt, flag
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)2 * B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (uint32_t p = 0; p < B; ++p)
+        if (h_cnt[(size_t)B + p]) {
+            const int rc = alone(p);
+            if (rc) return rc;
+            ++flagged;
+        }
+    if (getenv("MUMS_DEV_BATCH_REPORT"))   // development: the share of lists that ran alone
+        fprintf(stderr, "%s: %u lists, alone: %u before the tail, %u above %llu rows, %u with a full slice\n", who.c_str(), B,
+                before, above, (unsigned long long)kAnchorTailCap, flagged);
+    return batch_output(ctx, B, G, al, h_cnt.data(), d_doff, [&] {
+        return launch_anchor_emit(rt.V, rt.wlen, rt.ws, d_soff, d_cnt, d_doff, B, G, ctx->out_len.as<uint64_t>(),
+                                  ctx->out_s.as<int64_t>(), st);
+    }, M_out);
+}
+
+int mums_recursion_tail_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const uint64_t* match_off, const uint64_t* lengths,
+                              const int64_t* starts, uint32_t multiplicity, uint64_t min_length) {
+    if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (!have_device()) return fail(ctx, MUMS_E_NODEVICE, "no HIP device");
+    const std::string who = "mums_recursion_tail_batch";
+    if (ctx->shard || ctx->slice) return fail(ctx, MUMS_E_UNSUPPORTED, who + " on a sharded context");
+    if (G < 1) return fail(ctx, MUMS_E_INVALID, who + ": no sequences");
+    if (G > (uint32_t)kMaxG) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": more than 64 sequences per list");
+    if (B && !match_off) return fail(ctx, MUMS_E_INVALID, who + ": null list offsets");
+    for (uint32_t p = 0; p < B; ++p)
+        if (match_off[p + 1] < match_off[p]) return fail(ctx, MUMS_E_INVALID, who + ": list offsets decrease");
+    const uint64_t r0 = B ? match_off[0] : 0, Tt = B ? match_off[B] - r0 : 0;
+    if (Tt && (!lengths || !starts)) return fail(ctx, MUMS_E_INVALID, who + ": null MatchList");
+    if (Tt >= 0xFFFFFFF0ull) return fail(ctx, MUMS_E_UNSUPPORTED, who + ": 2^32 rows or more in one batch (split it)");
+    int rc = mums_clear(ctx);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    batch_vectors(ctx, B, true);
+    if (B == 0) return batch_done(ctx, G, 0, true);
+    hipStream_t st = ctx->stream;
+    (void)hipEventRecord(ctx->ev[EV_START], st);
+    std::vector<uint64_t> nrow(B);
+    for (uint32_t p = 0; p < B; ++p) ctx->anchor_table[p] = nrow[p] = match_off[p + 1] - match_off[p];
+    BatchAlone al;
+    al.routed.assign(B, 0);
+    al.rcount.assign(B, 0);
+    al.rfirst.assign(B, 0);
+    // the lists spread to their slices on the host, one upload each for lengths and starts
+    std::vector<int64_t> h_wlen, h_ws;
+    auto fill = [&](const std::vector<uint64_t>& soff, uint64_t*, uint32_t*, int64_t* d_wlen, int64_t* d_ws) -> hipError_t {
+        const uint64_t S = soff[B];
+        h_wlen.assign(S, 0);
+        h_ws.assign(S * (size_t)G, 0);
+        for (uint32_t p = 0; p < B; ++p) {
+            if (al.routed[p] || nrow[p] == 0) continue;
+            std::copy(lengths + match_off[p], lengths + match_off[p + 1], h_wlen.begin() + soff[p]);
+            std::copy(starts + match_off[p] * G, starts + match_off[p + 1] * G, h_ws.begin() + soff[p] * G);
+        }
+        hipError_t e = hipSuccess;
+        if (S) e = hipMemcpyAsync(d_wlen, h_wlen.data(), S * 8, hipMemcpyHostToDevice, st);
+        if (S && e == hipSuccess) e = hipMemcpyAsync(d_ws, h_ws.data(), S * (size_t)G * 8, hipMemcpyHostToDevice, st);
+        (void)hipEventRecord(ctx->ev[EV_KEYS], st);
+        return e;
+    };
+    auto job_of = [&](uint32_t p) {
+        AloneJob job{G};
+        job.n = nrow[p];
+        job.len = lengths + match_off[p];
+        job.s = starts + match_off[p] * G;
+        job.recursion = true;
+        job.multiplicity = multiplicity;
+        job.min_length = min_length;
+        return job;
+    };
+    uint64_t M = 0;
+    rc = recursion_tail_stage(ctx, who, B, G, nrow, al, multiplicity, min_length, fill, job_of, &M);
+    if (rc) return batch_abort(ctx, rc);
+    mums_stats& s = ctx->st;
+    s = mums_stats{};
+    s.mem_count = Tt;
+    s.ms_keys = batch_ms(ctx, EV_START, EV_KEYS);
+    s.ms_output = batch_ms(ctx, EV_KEYS, EV_OUTPUT);
+    s.ms_total = batch_ms(ctx, EV_START, EV_OUTPUT);
+    return batch_done(ctx, G, M, true);
+}
+
+int mums_recursion_batch(mums_ctx* ctx, uint32_t B, uint32_t G, const char* ascii, const uint64_t* seq_off,
+                         const uint64_t* patterns, uint32_t rounds, uint32_t multiplicity, uint64_t min_length) {
+    if (check_ctx(ctx)) return MUMS_E_INVALID;
+    if (!have_device()) return fail(ctx, MUMS_E_NODEVICE, "no HIP device");
+    const std::string who = "mums_recursion_batch";
+    int rc = batch_refusals(ctx, who, G);
+    if (rc) return rc;
+    if (rounds < 1 || rounds > 8) return fail(ctx, MUMS_E_INVALID, who + ": 1 to 8 rounds");
+    if (!patterns) return fail(ctx, MUMS_E_INVALID, who + ": null seed patterns");
+    BatchRun run{B, G, ascii, seq_off, true};
+    run.rd.resize(rounds);
+    for (uint32_t r = 0; r < rounds; ++r) {
+        if (patterns[r] == 0) return fail(ctx, MUMS_E_INVALID, who + ": a seed pattern is 0");
+        rc = batch_round(ctx, patterns[r], &run.rd[r]);
+        if (rc) return rc;
+    }
+    rc = batch_sequences_check(ctx, who, B, G, ascii, seq_off);
+    // the anchor path's constants: the v1 tail's own cost has not been measured
+    constexpr double kLaneUs = 18.0, kSingleUs = 915.0, kTailUs = 380.0;
+    if (!rc) rc = batch_plan(ctx, who, run, {kLaneUs, kSingleUs * (double)rounds + kTailUs});
+    if (rc) return rc;
+
+    // starts as MemHash::Clear does; the context's own seed pattern stays as it is
+    rc = mums_clear(ctx);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    batch_vectors(ctx, B, true);
+    if (B == 0) return batch_done(ctx, G, 0, true);
+
+    rc = batch_setup(ctx, run);
+    if (rc) return rc;
+    const uint64_t Nsum = run.pl.Nsum;
+    const uint64_t pool_cap64 = std::min<uint64_t>(Nsum / 2 + 1, std::max<uint64_t>(Nsum / 8, 1ull << 16));
+    rc = batch_rounds(ctx, run, run.pl.ord_words + 2, pool_cap64);
+    if (rc) return rc;
+    AloneJob job{G};
+    job.ascii = ascii;
+    job.patterns = patterns;
+    job.rounds = rounds;
+    job.recursion = true;
+    job.multiplicity = multiplicity;
+    job.min_length = min_length;
+    BatchAlone al;
+    rc = batch_fallbacks(ctx, who, run, job, al);
+    if (rc) return batch_abort(ctx, rc);
+    // the tail of the lanes' tables, gathered bucket-major into the first rows of their slices
+    std::vector<uint64_t> nrow(B, 0);
+    uint64_t T = 0;
+    for (uint32_t p = 0; p < B; ++p) T += nrow[p] = al.routed[p] ? 0 : run.per[p];
+    auto fill = [&](const std::vector<uint64_t>&, uint64_t* d_soff, uint32_t* d_nrow, int64_t* d_wlen, int64_t* d_ws) -> hipError_t {
+        if (T == 0) return hipSuccess;
+        return launch_anchor_gather(ctx->bt_ord.as<uint64_t>(), run.d_obase, ctx->bt_pool.as<int64_t>(), d_soff, B, G, d_wlen,
+                                    d_ws, ctx->stream, d_nrow);
+    };
+    auto job_of = [&](uint32_t p) {   // from round 0: the rounds and the tail on the problem's sequences
+        AloneJob j = job;
+        j.so = seq_off + (uint64_t)p * G;
+        return j;
+    };
+    uint64_t M = 0, E = 0;
+    rc = recursion_tail_stage(ctx, who, B, G, nrow, al, multiplicity, min_length, fill, job_of, &M);
+    if (rc) return batch_abort(ctx, rc);
+    for (uint32_t p = 0; p < B; ++p) E += ctx->anchor_table[p];
+    batch_stats(ctx, run, E);
+    return batch_done(ctx, G, M, true);
 }
 
 // test entry point: the device replay of libstdc++ std::sort (overlaps.hip) on host keys

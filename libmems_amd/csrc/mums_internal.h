@@ -750,9 +750,11 @@ hipError_t launch_batch_emit(const uint64_t* ord, const int64_t* pool, const uin
 // anchor.hip: pairwiseAnchorSearch's tail (EliminateOverlaps_v2 over every sequence, then
 // LengthFilter) for B lists in one pass.  List p = rows [toff[p], toff[p + 1]) of wlen / ws
 // (lengths, G starts per row; cropped in place).
-// problem p's table (ord slice at obase[p], entries in pool: batch.hip) -> its rows of wlen / ws
+// problem p's table (ord slice at obase[p], entries in pool: batch.hip) -> its rows of wlen / ws;
+// nrow (recursion.hip's slices, wider than the table): the table's rows, at toff[p]
 hipError_t launch_anchor_gather(const uint64_t* ord, const uint32_t* obase, const int64_t* pool, const uint64_t* toff,
-                                uint32_t B, uint32_t G, int64_t* wlen, int64_t* ws, hipStream_t st);
+                                uint32_t B, uint32_t G, int64_t* wlen, int64_t* ws, hipStream_t st,
+                                const uint32_t* nrow = nullptr);
 struct AnchorTail {
     uint64_t* K;              // toff[B] words of scratch: sort keys
     uint32_t* V;              // toff[B] words: out, list p's surviving row ids (list-local) at V[toff[p] ..]
@@ -771,6 +773,28 @@ hipError_t launch_anchor_tail(const AnchorTail& a, hipStream_t st);
 hipError_t launch_anchor_emit(const uint32_t* V, const int64_t* wlen, const int64_t* ws, const uint64_t* toff,
                               const uint32_t* cnt, const uint64_t* doff, uint32_t B, uint32_t G, uint64_t* out_len,
                               int64_t* out_s, hipStream_t st);
+
+// recursion.hip: Aligner::Recursion's tail (EliminateOverlaps v1, MultiplicityFilter, LengthFilter)
+// for B lists in one pass.  v1 appends rows, so list p owns the slice [soff[p], soff[p + 1]) of
+// wlen / ws / K / V (recursion_slice_rows(input rows, G) of them); its input is the first nrow[p] rows.
+uint64_t recursion_slice_rows(uint64_t n, uint32_t G);
+struct RecursionTail {
+    uint64_t* K;              // soff[B] words of scratch: sort keys
+    uint32_t* V;              // soff[B] words: out, list p's surviving row ids (slice-local) at V[soff[p] ..]
+    int64_t* wlen;
+    int64_t* ws;
+    const uint64_t* soff;     // B + 1
+    const uint32_t* nrow;     // B: input rows
+    const uint32_t* order;    // lane -> problem (lists of similar size share a wave)
+    const uint8_t* skip;      // B: 1 = not run here (cnt[p] = 0)
+    uint32_t* cnt;            // B: surviving rows
+    uint32_t* flag;           // B: 1 = a copy did not fit the slice (cnt[p] = 0, the list runs alone)
+    uint32_t B, G;
+    uint32_t multiplicity;    // 0: no MultiplicityFilter
+    uint64_t min_length;
+};
+// (the rows go to the MatchList through launch_anchor_emit, with soff as its toff)
+hipError_t launch_recursion_tail(const RecursionTail& a, hipStream_t st);
 
 // smlsort.hip: the std::sort order of equal seed mers in every SortedMerList
 // (MemorySML.cpp:54) for flagged runs.  Slot space = genome-major SML slots (= global

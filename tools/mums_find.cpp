@@ -19,6 +19,13 @@
 //       from the loop of pairwiseAnchorSearch (Clear; per rank ClearSequences + FindMatches;
 //       EliminateOverlaps_v2; LengthFilter(12)) on the same object, then after "== tail" from
 //       AnchorTailBatch over the problems' family tables
+//   mums_find recursion files G nway weights f0_0 .. f0_G-1 f1_0 ...   one gap problem of Aligner::Recursion
+//       per G files; nway: 0 / 1 (nway_only); weights: w0,w1,...,wG-1 for every problem's sequences or
+//       "default" (getDefaultSeedWeight of each length).  "# problem k" + its list, first from
+//       MemHash::RecursionBatch, then after "== loop" from the loop of Recursion's calls (Clear; per
+//       round ClearSequences + FindMatches; EliminateOverlaps; MultiplicityFilter when nway;
+//       LengthFilter(9)) on the same object, then after "== tail" from RecursionTailBatch over the
+//       problems' tables
 //   mums_find smldump G n weight p g stride  genome g's deferred SML read back: every entry
 //       (position, mer) through operator[], then FindMer of every stride-th entry's mer
 #include <unistd.h>
@@ -233,6 +240,74 @@ int main(int argc, char** argv) {
             for (int k = 0; k < B; ++k) {
                 os << "# problem " << k << '\n';
                 for (const auto& m : tails[k]) os << m << '\n';
+            }
+            std::cout << os.str();
+            std::cerr << "problems " << B << " table entries " << entries << "\n";
+        } catch (const std::exception& e) {
+            std::cerr << "error: " << e.what() << "\n";
+            return 1;
+        }
+        return 0;
+    }
+    if (mode == "recursion" && argc >= 7 && std::string(argv[2]) == "files") {
+        const int G = atoi(argv[3]);
+        const bool nway = atoi(argv[4]) != 0;
+        const std::string wspec = argv[5];
+        if (G < 2 || (argc - 6) % G != 0) {
+            std::cerr << "error: recursion files G nway weights, then G files per problem\n";
+            return 2;
+        }
+        const int B = (argc - 6) / G;
+        try {
+            std::vector<std::vector<std::string>> problems((size_t)B);
+            for (int k = 0; k < B; ++k)
+                for (int g = 0; g < G; ++g) problems[(size_t)k].push_back(read_seq(argv[6 + k * G + g]));
+            std::vector<std::vector<uint32_t>> weights((size_t)B);
+            for (int k = 0; k < B; ++k) {
+                if (wspec == "default") {
+                    for (const std::string& q : problems[(size_t)k]) weights[(size_t)k].push_back(mums_default_seed_weight(q.size()));
+                } else {
+                    std::stringstream ws(wspec);
+                    std::string tok;
+                    while (std::getline(ws, tok, ',')) weights[(size_t)k].push_back((uint32_t)atoi(tok.c_str()));
+                }
+            }
+            mums::MemHash mh(0);
+            std::vector<mums::MatchList> lists, tables((size_t)B), tails;
+            mh.RecursionBatch(problems, lists, nway, 9, weights);
+            std::ostringstream os;
+            uint64_t entries = 0;
+            for (uint64_t v : mh.AnchorBatchInfo().table_entries) entries += v;
+            for (int k = 0; k < B; ++k) {
+                os << "# problem " << k << '\n';
+                for (const auto& m : lists[(size_t)k]) os << m << '\n';
+            }
+            os << "== loop\n";
+            for (int k = 0; k < B; ++k) {
+                os << "# problem " << k << '\n';
+                const std::vector<uint32_t> rounds = mums::MemHash::recursion_rounds(weights[(size_t)k], nway);
+                if (rounds.empty()) continue;
+                mh.Clear();
+                mums::MatchList ml;
+                for (uint32_t w : rounds) {
+                    mh.ClearSequences();
+                    mh.SetSeed((uint64_t)mums_get_seed((int)w, 0));
+                    ml.clear();
+                    ml.seq_table = problems[(size_t)k];
+                    mh.FindMatches(ml);
+                }
+                mh.GetMatchList(tables[(size_t)k]);
+                mh.EliminateOverlaps();
+                if (nway) mh.MultiplicityFilter((unsigned)G);
+                mh.LengthFilter(9);
+                mh.GetMatchList(ml);
+                for (const auto& m : ml) os << m << '\n';
+            }
+            os << "== tail\n";
+            mh.RecursionTailBatch(tables, (uint32_t)G, tails, nway ? (uint32_t)G : 0, 9);
+            for (int k = 0; k < B; ++k) {
+                os << "# problem " << k << '\n';
+                for (const auto& m : tails[(size_t)k]) os << m << '\n';
             }
             std::cout << os.str();
             std::cerr << "problems " << B << " table entries " << entries << "\n";
