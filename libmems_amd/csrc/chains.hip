@@ -46,20 +46,6 @@ namespace {
 #define MUMS_WALK_BUDGET 8
 #endif
 constexpr int kWalkBudget = MUMS_WALK_BUDGET;   // words per lane in chain_walk_short_kernel
-#ifndef MUMS_WALK_SORT_SHIFT
-#define MUMS_WALK_SORT_SHIFT 11
-#endif
-constexpr int kWalkSortShift = MUMS_WALK_SORT_SHIFT;   // walk order granule: 2^11 columns
-#ifndef MUMS_WALK_SWZ
-#define MUMS_WALK_SWZ 0   // 1: walk kernels in XCD-grouped block order (measured slower)
-#endif
-__device__ __forceinline__ unsigned walk_block() {
-#if MUMS_WALK_SWZ
-    return xcd_grouped_block(blockIdx.x, gridDim.x);
-#else
-    return blockIdx.x;
-#endif
-}
 // waves per SIMD the walk kernels are compiled for (0: the compiler's choice, 3 at MG = 8 --
 // ~150 VGPRs); more waves keep more of the walks' dependent loads in flight
 #ifndef MUMS_WALK_WPE
@@ -554,34 +540,6 @@ __global__ __launch_bounds__(kBlock) void chain_left_kernel(uint64_t P, const ui
     block_push<kLinkIPT>(want, it, queue, qcount);
 }
 
-// Walk order by genome position: record (x >> shift) << 32 | q of queue item q, x = the
-// first start of its probe.  A walk reads the packed windows of every component around its
-// probe -- about one 128-B line per genome per walk, lines that the walks of nearby probes
-// (other lines of the same region: the partial tuples around a substitution, the next chain
-// of the diagonal) read too.  In line order those walks are far apart in time and each line
-// is fetched again from HBM; sorted by position they run close together and share L2.
-template <int MG, typename View>
-__global__ __launch_bounds__(kBlock) void walk_key_kernel(View v, GenomeTable gt, MatchParams mp, int L,
-                                                          const WalkItem* __restrict__ queue,
-                                                          const unsigned int* __restrict__ qcount, int shift,
-                                                          uint64_t* __restrict__ rec) {
-    const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (q >= *qcount) return;
-    Mhe<MG> A;
-    probe_of<MG, View>(v, nullptr, queue[q].j, gt, mp, L, A);
-    const int64_t x = start_at(A, first_start(A));
-    rec[q] = ((uint64_t)(x > 0 ? x : 0) >> shift << 32) | q;
-}
-
-// records (j << 32 | i) of the handed-on walks: their line order back (MUMS_DEV_WALK_SORT=2)
-__global__ __launch_bounds__(kBlock) void walk_line_key_kernel(const WalkItem* __restrict__ lq,
-                                                               const unsigned int* __restrict__ lqcount,
-                                                               uint64_t* __restrict__ rec) {
-    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= *lqcount) return;
-    rec[i] = ((uint64_t)lq[i].j << 32) | i;
-}
-
 // Queued walks, one lane per item, up to kWalkBudget 64-column words each (most chain ends
 // lie within a few words); the rest go on to chain_walk_kernel's lane groups.
 template <int MG, typename View, bool kGen = true>
@@ -593,7 +551,6 @@ __global__ __launch_bounds__(kBlock) MUMS_WALK_ATTR void chain_walk_short_kernel
                                                                   uint8_t* __restrict__ link, int64_t* __restrict__ rcol,
                                                                   int64_t* __restrict__ lcol, WalkItem* __restrict__ lq,
                                                                   unsigned int* __restrict__ lqcount,
-                                                                  const uint64_t* __restrict__ order,
                                                                   DevCounters* __restrict__ ctr) {
     const int L = ss.L;
     const LineSpec ls = line_spec(ss, gt);
@@ -601,12 +558,12 @@ __global__ __launch_bounds__(kBlock) MUMS_WALK_ATTR void chain_walk_short_kernel
     const unsigned stride = gridDim.x * kBlock;
     uint32_t my_words = 0, my_items = 0, my_wins = 0;   // (a lane's walks: a few, <= kWalkBudget words each)
     // block-uniform trip count: block_push synchronises the workgroup
-    for (unsigned q0 = walk_block() * kBlock; q0 < nq; q0 += stride) {
+    for (unsigned q0 = blockIdx.x * kBlock; q0 < nq; q0 += stride) {
         const unsigned q = q0 + threadIdx.x;
         uint32_t want = 0;
         WalkItem nx[1] = {WalkItem{}};
         if (q < nq) {
-            const WalkItem it = queue[order ? (uint32_t)order[q] : q];
+            const WalkItem it = queue[q];
             Mhe<MG> A;
             probe_of<MG, View>(v, probe_info, it.j, gt, mp, L, A);
             const int64_t xa = start_at(A, first_start(A));
@@ -652,111 +609,6 @@ __global__ __launch_bounds__(kBlock) MUMS_WALK_ATTR void chain_walk_short_kernel
     }
 }
 
-// chain_walk_short_kernel with lane refill.  Walk lengths are heavy-tailed (about one item
-// in five spends the whole budget), so a wave of 64 one-shot lanes nearly always runs
-// kWalkBudget steps for items that mostly end after one or two words.  Here each block owns
-// a contiguous range of the queue, a lane whose walk has ended takes the next item of that
-// range (LDS counter, once kRefillMin lanes of the wave are idle) and every step advances
-// each busy lane by one word.  Results per item are the same as chain_walk_short_kernel's
-// (same walk, same budget); the handed-on items reach lq in another order, which no later
-// step depends on.
-#ifndef MUMS_WALK_REFILL_MIN
-#define MUMS_WALK_REFILL_MIN 16
-#endif
-template <int MG, typename View>
-__global__ __launch_bounds__(kBlock) void chain_walk_refill_kernel(View v, GenomeTable gt, MatchParams mp, SeedSpec ss,
-                                                                   const uint32_t* __restrict__ packed,
-                                                                   const WalkItem* __restrict__ queue,
-                                                                   const unsigned int* __restrict__ qcount,
-                                                                   uint8_t* __restrict__ link, int64_t* __restrict__ rcol,
-                                                                   int64_t* __restrict__ lcol, WalkItem* __restrict__ lq,
-                                                                   unsigned int* __restrict__ lqcount) {
-    const int L = ss.L;
-    const LineSpec ls = line_spec(ss, gt);
-    const unsigned nq = *qcount;
-    const unsigned per = (nq + gridDim.x - 1) / gridDim.x;
-    const unsigned lo = min(nq, blockIdx.x * per), hi = min(nq, lo + per);
-    __shared__ unsigned s_next;
-    if (threadIdx.x == 0) s_next = lo;
-    __syncthreads();
-    if (lo >= hi) return;
-    const int lane = threadIdx.x & 63;
-    const uint64_t below = (1ull << lane) - 1;
-    bool have = false, more = true;   // more: wave-uniform
-    WalkItem it{};
-    Mhe<MG> A;
-    int64_t xa = 0, clo = 0, chi = 0, last = 0, u0 = 1;
-    int budget = 0, dir = 1;
-    for (;;) {
-        const uint64_t idle = __ballot(!have);
-        const unsigned n = (unsigned)__popcll(idle);
-        if (more && n >= (unsigned)MUMS_WALK_REFILL_MIN) {
-            const int lead = __builtin_ctzll(idle);
-            unsigned base = 0;
-            if (lane == lead) base = atomicAdd(&s_next, n);
-            base = __shfl(base, lead);
-            if (base + n >= hi) more = false;
-            if (!have) {
-                const unsigned q = base + (unsigned)__popcll(idle & below);
-                if (q < hi) {
-                    it = queue[q];
-                    probe_of<MG, View>(v, nullptr, it.j, gt, mp, L, A);
-                    xa = start_at(A, first_start(A));
-                    frame_bounds<MG>(A, gt, &clo, &chi);
-                    dir = it.kind == 2 ? -1 : +1;
-                    last = 0;
-                    u0 = 1;
-                    budget = kWalkBudget;
-                    have = true;
-                }
-            }
-        }
-        if (!__any(have)) {
-            if (!more) break;
-            continue;
-        }
-        bool hand_on = false;
-        if (have) {   // one step of walk_lane
-            const int64_t col = it.cur + dir * last;
-            int state = -1;
-            int64_t c = col;
-            if (dir > 0 ? col >= it.stop : col <= it.stop) state = 1;
-            else if (budget-- <= 0) state = 2;
-            else {
-                const uint64_t H = hit_word_dir<MG>(dir, it.cur + dir * u0, A, gt, clo, chi, packed, ss, ls);
-                const bool broke = scan_word(H, u0, &last, L);
-                u0 += 64;
-                if (broke) {
-                    c = it.cur + dir * last;
-                    state = (dir > 0 ? c >= it.stop : c <= it.stop) ? 1 : 0;
-                }
-            }
-            if (state >= 0) {
-                have = false;
-                if (state == 2) {
-                    hand_on = true;
-                    it.cur = c;
-                } else if (it.kind == 0) {
-                    link[it.j] = state == 1 ? 1 : 0;
-                    if (state == 0) rcol[it.j] = xa + c;
-                } else if (it.kind == 1) {
-                    rcol[it.j] = xa + c;
-                } else {
-                    lcol[it.j] = xa + c;
-                }
-            }
-        }
-        const uint64_t hm = __ballot(hand_on);
-        if (hm) {   // wave-aggregated append to the long-walk queue
-            const int lead = __builtin_ctzll(hm);
-            unsigned base = 0;
-            if (lane == lead) base = atomicAdd(lqcount, (unsigned)__popcll(hm));
-            base = __shfl(base, lead);
-            if (hand_on) lq[base + (unsigned)__popcll(hm & below)] = it;
-        }
-    }
-}
-
 // Long walks, one group of kWalkGroup lanes per item (grid-stride over the queue; a wave
 // walks 64 / kWalkGroup items at once: most queued walks end within a few words, so more
 // items in flight hide more load latency than wider steps would).  Each step evaluates the
@@ -787,8 +639,7 @@ __global__ __launch_bounds__(kBlock) MUMS_WALK_ATTR MUMS_WALK_LEAN_ATTR void cha
                                                             uint8_t* __restrict__ link, int64_t* __restrict__ rcol,
                                                             int64_t* __restrict__ lcol, unsigned int* __restrict__ dbg,
                                                             DevCounters* __restrict__ ctr, unsigned maxsteps,
-                                                            WalkItem* __restrict__ xq, unsigned int* __restrict__ xqcount,
-                                                            const uint64_t* __restrict__ order) {
+                                                            WalkItem* __restrict__ xq, unsigned int* __restrict__ xqcount) {
     static_assert(GS >= 2 && GS <= 64 && (GS & (GS - 1)) == 0, "group: power of 2");
     unsigned long long my_words = 0, my_items = 0, my_wins = 0;
     const int lane = threadIdx.x & 63, gl = lane & (GS - 1), gsh = lane & ~(GS - 1);
@@ -797,8 +648,8 @@ __global__ __launch_bounds__(kBlock) MUMS_WALK_ATTR MUMS_WALK_LEAN_ATTR void cha
     const LineSpec ls = line_spec(ss, gt);
     const unsigned nq = *qcount;
     const unsigned ngroups = gridDim.x * (kBlock / GS);
-    for (unsigned qi = (walk_block() * kBlock + threadIdx.x) / GS; qi < nq; qi += ngroups) {
-        const WalkItem it = queue[order ? (uint32_t)order[qi] : qi];
+    for (unsigned qi = (blockIdx.x * kBlock + threadIdx.x) / GS; qi < nq; qi += ngroups) {
+        const WalkItem it = queue[qi];
         Mhe<MG> A;
         probe_of<MG, View>(v, probe_info, it.j, gt, mp, L, A);
         const int64_t xa = start_at(A, first_start(A));
@@ -993,13 +844,6 @@ __global__ __launch_bounds__(kBlock) void line_rec2_kernel(const uint32_t* __res
     }
 }
 
-__global__ __launch_bounds__(kBlock) void line_ord_kernel(const uint64_t* __restrict__ s1,
-                                                          const uint64_t* __restrict__ s2, uint64_t P,
-                                                          uint32_t* __restrict__ ord) {
-    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j < P) ord[j] = (uint32_t)s1[(uint32_t)s2[j]];
-}
-
 // the rows in line order as LineRows (match_device.h): a block's kBlock rows are loaded
 // element-wise (neighbouring lanes on one row, all loads in flight together) into LDS, then
 // each thread packs one row's starts to int32 and checks that they fit and that the
@@ -1052,23 +896,6 @@ __global__ __launch_bounds__(kBlock) void gather_line_rows_kernel(const int64_t*
             *reinterpret_cast<int4*>(out + 4 * q) =
                 make_int4((int32_t)Q.s[4 * q], (int32_t)Q.s[4 * q + 1], (int32_t)Q.s[4 * q + 2], (int32_t)Q.s[4 * q + 3]);
     if (!ok) atomicOr(bad, 1u);
-}
-
-// int32 rows (MatProbes::rows32) in line order: row ord[j] -> row j, S / 4 int4 per row
-__global__ __launch_bounds__(kBlock) void gather_rows32_kernel(const int32_t* __restrict__ src,
-                                                               const uint32_t* __restrict__ ord, uint64_t P,
-                                                               uint32_t S, int32_t* __restrict__ dst) {
-    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j >= P) return;
-    const int4* a = reinterpret_cast<const int4*>(src + (uint64_t)ord[j] * S);
-    int4* b = reinterpret_cast<int4*>(dst + j * S);
-    if (S == 8) {
-        const int4 x = a[0], y = a[1];
-        b[0] = x;
-        b[1] = y;
-    } else {
-        for (uint32_t q = 0; q < S / 4; ++q) b[q] = a[q];
-    }
 }
 
 inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
@@ -1270,25 +1097,16 @@ hipError_t line_sort(const ChainWs& w, uint64_t P, int xbits, void* d_tmp, uint3
     if ((e = seg_onesweep_sort(w.kA, w.kB, P, xbits, 0, w.bst, d_tmp, d_err, &b1, st)) != hipSuccess) return e;
     const uint64_t* s1 = b1 ? w.kB : w.kA;
     uint64_t* r2 = b1 ? w.kA : w.kB;
-    const bool fused_hist = kLineHashBits == 32 && !getenv("MUMS_DEV_LINE_GHIST");   // read per call
     if ((e = hipMemsetAsync(w.hh, 0, 4 * 256 * 4, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(line_rec2_kernel, dim3((unsigned)std::min<uint64_t>(grid_of(P), 4096)), dim3(kBlock), 0, st,
                        (const uint32_t*)w.vB, s1, P, r2, w.hh);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     int b2 = 0;
-    // the hashes in x order come in runs (a line's probes): run-aware histogram, late publish
-    const bool runs = !getenv("MUMS_DEV_LINE_NORUNS");   // read per call (tests toggle it)
-    // the last hash pass stores ord[o] = probe of s1[j] directly (MUMS_DEV_LINE_ORD=1, read per
-    // call: the records, then line_ord_kernel's gather)
-    const bool fused_ord = runs && !getenv("MUMS_DEV_LINE_ORD");
+    // the hashes in x order come in runs (a line's probes): run-aware histogram, late publish;
+    // the last hash pass stores ord[o] = probe of s1[j] directly
     if ((e = seg_onesweep_sort(r2, w.lkey, P, kLineHashBits, 0, w.bst, d_tmp, d_err, &b2, st, nullptr, 32, false,
-                               runs, fused_hist ? w.hh : nullptr, fused_ord ? s1 : nullptr,
-                               fused_ord ? w.vA : nullptr)) != hipSuccess)
+                               true, kLineHashBits == 32 ? w.hh : nullptr, s1, w.vA)) != hipSuccess)
         return e;
-    if (!fused_ord) {
-        const uint64_t* s2 = b2 ? w.lkey : r2;
-        hipLaunchKernelGGL(line_ord_kernel, dim3(grid_of(P)), dim3(kBlock), 0, st, s1, s2, P, w.vA);
-    }
     *ord_out = w.vA;
     return hipGetLastError();
 }
@@ -1306,8 +1124,8 @@ int x_bits(const GenomeTable& gt) {
 template <int MG, typename LV>
 hipError_t chains_core(LV vl, const ChainWs& w, const uint32_t* ord, uint64_t P, const GenomeTable& gt,
                        const MatchParams& mp, const SeedSpec& ss, const uint32_t* packed, void* d_scan_tmp,
-                       void* d_radix_tmp, uint32_t* chain_of, int64_t* pool, uint32_t* d_nchains, hipStream_t st,
-                       void* ctr, hipEvent_t* ev_walk, uint32_t* fk, uint32_t kbase, uint32_t* jl) {
+                       uint32_t* chain_of, int64_t* pool, uint32_t* d_nchains, hipStream_t st, void* ctr,
+                       hipEvent_t* ev_walk, uint32_t* fk, uint32_t kbase, uint32_t* jl) {
     hipError_t e;
     const unsigned grid = grid_of(P);
     const unsigned walk_grid = 2048, short_grid = 8192;
@@ -1315,23 +1133,9 @@ hipError_t chains_core(LV vl, const ChainWs& w, const uint32_t* ord, uint64_t P,
     unsigned int* qshort = qcount;      // chain_link / chain_left -> chain_walk_short_kernel
     unsigned int* qlong = qcount + 1;   // chain_walk_short_kernel -> chain_walk_kernel
     const bool cdbg = getenv("MUMS_DEV_CHAIN_DEBUG") != nullptr;
-    // refilled short-walk lanes (read per call: tests and A/B runs toggle it)
-    const bool refill = getenv("MUMS_DEV_WALK_REFILL") && getenv("MUMS_DEV_WALK_REFILL")[0] == '1';
     // the walks without the generic hit-word path when every window is tested by base comparison
     // (palindromic care set, odd weight: hit_word<MG, false>); MUMS_DEV_WALK_GEN=1 keeps it
     const bool lean = seed_bitpar_odd(ss) && !(getenv("MUMS_DEV_WALK_GEN") && getenv("MUMS_DEV_WALK_GEN")[0] == '1');
-    // short walks in genome-position order (walk_key_kernel), MUMS_DEV_WALK_SORT=1: measured
-    // slower at C3 than the queue's line order, kept for A/B runs
-    const char* wsort_env = getenv("MUMS_DEV_WALK_SORT");
-    const bool wsort = !refill && wsort_env && (wsort_env[0] == '1' || wsort_env[0] == '2') && P < (1ull << 32);
-    const bool wsort_long = wsort && wsort_env[0] == '2';   // and the handed-on walks back in line order
-    int pbits = 1;
-    while (pbits < 32 && (1ull << pbits) < P) ++pbits;
-    // (MUMS_DEV_WALK_SHIFT, read per call: the granule of that order, development A/B)
-    const char* wsh_env = getenv("MUMS_DEV_WALK_SHIFT");
-    const int wshift = wsh_env ? std::max(0, std::min(31, atoi(wsh_env))) : kWalkSortShift;
-    const int wbits = std::max(1, x_bits(gt) - wshift);
-    uint32_t* d_err = ctr ? &((DevCounters*)ctr)->err : w.qcount + 14;
     for (int pass = 0; pass < 2; ++pass) {
         if ((e = hipMemsetAsync(qcount, 0, 12, st)) != hipSuccess) return e;
         const unsigned lgrid = (unsigned)((P + kBlock * kLinkIPT - 1) / (kBlock * kLinkIPT));
@@ -1342,71 +1146,31 @@ hipError_t chains_core(LV vl, const ChainWs& w, const uint32_t* ord, uint64_t P,
             hipLaunchKernelGGL(chain_left_kernel, dim3(lgrid), dim3(kBlock), 0, st, P, (const uint8_t*)w.link, w.queue,
                                qshort, w.seg);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        const uint64_t* order = nullptr;
-        if (wsort) {   // the queue length sizes the sort: read back (one small sync per pass)
-            unsigned nq = 0;
-            if ((e = hipMemcpyAsync(&nq, qshort, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-            if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-            if (nq > 1) {
-                hipLaunchKernelGGL((walk_key_kernel<MG, LV>), dim3(grid_of(nq)), dim3(kBlock), 0, st, vl, gt, mp, ss.L,
-                                   (const WalkItem*)w.queue, (const unsigned int*)qshort, wshift, w.kA);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                if ((e = seg_bucket_starts(nullptr, 0, 0, nq, w.bst + 8, st)) != hipSuccess) return e;
-                int ob = 0;
-                if ((e = seg_onesweep_sort(w.kA, w.kB, nq, wbits, 0, w.bst + 8, d_radix_tmp, d_err, &ob, st)) !=
-                    hipSuccess)
-                    return e;
-                order = ob ? w.kB : w.kA;
-            }
-        }
         if (ev_walk) (void)hipEventRecord(ev_walk[3 * pass], st);   // the short walks start
-        if (refill)
-            hipLaunchKernelGGL((chain_walk_refill_kernel<MG, LV>), dim3(short_grid), dim3(kBlock), 0, st, vl, gt, mp,
-                               ss, packed, (const WalkItem*)w.queue, (const unsigned int*)qshort, w.link, w.rcol,
-                               w.lcol, w.queue_long, qlong);
-        else if (lean)
+        if (lean)
             hipLaunchKernelGGL((chain_walk_short_kernel<MG, LV, false>), dim3(short_grid), dim3(kBlock), 0, st, vl,
                                nullptr, gt, mp, ss, packed, (const WalkItem*)w.queue, (const unsigned int*)qshort,
-                               w.link, w.rcol, w.lcol, w.queue_long, qlong, order, (DevCounters*)ctr);
+                               w.link, w.rcol, w.lcol, w.queue_long, qlong, (DevCounters*)ctr);
         else
             hipLaunchKernelGGL((chain_walk_short_kernel<MG, LV>), dim3(short_grid), dim3(kBlock), 0, st, vl, nullptr,
                                gt, mp, ss, packed, (const WalkItem*)w.queue, (const unsigned int*)qshort, w.link,
-                               w.rcol, w.lcol, w.queue_long, qlong, order, (DevCounters*)ctr);
+                               w.rcol, w.lcol, w.queue_long, qlong, (DevCounters*)ctr);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (cdbg && (e = hipMemsetAsync(qcount + 4, 0, 32, st)) != hipSuccess) return e;
         if (ev_walk) (void)hipEventRecord(ev_walk[3 * pass + 1], st);
-        const uint64_t* lorder = nullptr;
-        if (wsort_long && order) {
-            unsigned nl = 0;
-            if ((e = hipMemcpyAsync(&nl, qlong, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-            if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-            if (nl > 1) {
-                uint64_t* ra = order == w.kA ? w.kB : w.kA;   // the short walks' order is consumed
-                uint64_t* rb = order == w.kA ? w.kA : w.kB;
-                hipLaunchKernelGGL(walk_line_key_kernel, dim3(grid_of(nl)), dim3(kBlock), 0, st,
-                                   (const WalkItem*)w.queue_long, (const unsigned int*)qlong, ra);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                if ((e = seg_bucket_starts(nullptr, 0, 0, nl, w.bst + 8, st)) != hipSuccess) return e;
-                int ob = 0;
-                if ((e = seg_onesweep_sort(ra, rb, nl, pbits, 0, w.bst + 8, d_radix_tmp, d_err, &ob, st)) !=
-                    hipSuccess)
-                    return e;
-                lorder = ob ? rb : ra;
-            }
-        }
         // the queue of chain_link / chain_left is consumed: it takes the handed-on walks
 #define MUMS_WALK_LAUNCH(GEN)                                                                                     \
     do {                                                                                                             \
         hipLaunchKernelGGL((chain_walk_kernel<MG, LV, kWalkGroup, GEN>), dim3(walk_grid), dim3(kBlock), 0, st, vl,  \
                            nullptr, gt, mp, ss, ord, packed, (const WalkItem*)w.queue_long, (const unsigned int*)qlong, \
                            w.link, w.rcol, w.lcol, cdbg ? qcount + 4 : nullptr, (DevCounters*)ctr, kWalkHandoff,     \
-                           w.queue, qcount + 2, lorder);                                                             \
+                           w.queue, qcount + 2);                                                                     \
         if ((e = hipGetLastError()) != hipSuccess) return e;                                                         \
         if (kWalkHandoff)                                                                                            \
             hipLaunchKernelGGL((chain_walk_kernel<MG, LV, 64, GEN>), dim3(walk_grid), dim3(kBlock), 0, st, vl, nullptr, \
                                gt, mp, ss, ord, packed, (const WalkItem*)w.queue, (const unsigned int*)(qcount + 2), \
                                w.link, w.rcol, w.lcol, cdbg ? qcount + 4 : nullptr, (DevCounters*)ctr, 0u,           \
-                               (WalkItem*)nullptr, (unsigned int*)nullptr, (const uint64_t*)nullptr);               \
+                               (WalkItem*)nullptr, (unsigned int*)nullptr);                                         \
     } while (0)
         if (lean) MUMS_WALK_LAUNCH(false);
         else MUMS_WALK_LAUNCH(true);
@@ -1543,37 +1307,28 @@ hipError_t launch_chains(View v, const uint64_t* probe_info, uint64_t P, const G
         hipError_t r;
         if ((r = hipMemsetAsync(flags, 0, 8, st)) != hipSuccess) return r;
         if constexpr (MG % 4 == 0 && MG <= 16) {
-            // the int32 rows are read through the line order (chain_link shares each row with its
-            // neighbour lane): 1.3 ms less than gathering them at C3;
-            // MUMS_DEV_LINE_GATHER=1 (read per call) gathers them first
-            const char* lg = getenv("MUMS_DEV_LINE_GATHER");
-            if (v.rows32 && !(lg && lg[0] == '1')) {
+            // the int32 rows in key order (materialize_dispatch) are read through the line order
+            // (chain_link shares each row with its neighbour lane): 1.3 ms less than gathering
+            // them at C3
+            if (v.rows32) {
                 LineRows vl{v.rows32, v.stride32, v.L32, o};
-                return chains_core<MG>(vl, w, o, P, gt, mp, ss, packed, d_scan_tmp, d_radix_tmp, chain_of, pool,
-                                       d_nchains, st, ctr, ev_walk, fk, kbase, jl);
-            }
-            if (v.rows32) {   // int32 rows in key order (materialize_dispatch): copied in line order
-                hipLaunchKernelGGL(gather_rows32_kernel, dim3(grid_of(P)), dim3(kBlock), 0, st, v.rows32, o, P,
-                                   v.stride32, (int32_t*)w.rows_line);
-                if ((r = hipGetLastError()) != hipSuccess) return r;
-                LineRows vl{(const int32_t*)w.rows_line, v.stride32, v.L32};
-                return chains_core<MG>(vl, w, o, P, gt, mp, ss, packed, d_scan_tmp, d_radix_tmp, chain_of, pool, d_nchains, st, ctr,
-                                       ev_walk, fk, kbase, jl);
+                return chains_core<MG>(vl, w, o, P, gt, mp, ss, packed, d_scan_tmp, chain_of, pool, d_nchains, st,
+                                       ctr, ev_walk, fk, kbase, jl);
             }
             if (narrow) {
                 hipLaunchKernelGGL((gather_line_rows_kernel<MG>), dim3(grid_of(P)), dim3(kBlock), 0, st, v.rows, o, P,
                                    gt.G, ss.L, (int32_t*)w.rows_line, flags + 1);
                 if ((r = hipGetLastError()) != hipSuccess) return r;
                 LineRows vl{(const int32_t*)w.rows_line, line_row_stride(gt.G), ss.L};
-                return chains_core<MG>(vl, w, o, P, gt, mp, ss, packed, d_scan_tmp, d_radix_tmp, chain_of, pool, d_nchains, st, ctr,
-                                       ev_walk, fk, kbase, jl);
+                return chains_core<MG>(vl, w, o, P, gt, mp, ss, packed, d_scan_tmp, chain_of, pool, d_nchains, st,
+                                       ctr, ev_walk, fk, kbase, jl);
             }
         }
         if ((r = launch_gather_rows(v.rows, o, P, gt.G, w.rows_line, st)) != hipSuccess) return r;
         MatProbes vl{};
         vl.rows = w.rows_line;
-        return chains_core<MG>(vl, w, o, P, gt, mp, ss, packed, d_scan_tmp, d_radix_tmp, chain_of, pool, d_nchains, st, ctr, ev_walk,
-                               fk, kbase, jl);
+        return chains_core<MG>(vl, w, o, P, gt, mp, ss, packed, d_scan_tmp, chain_of, pool, d_nchains, st, ctr,
+                               ev_walk, fk, kbase, jl);
     };
     unsigned hf[2] = {0, 0};
     auto read_flags = [&]() -> hipError_t {

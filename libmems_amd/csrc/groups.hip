@@ -573,23 +573,6 @@ __global__ __launch_bounds__(kBlock) void gather_rows_ilp_kernel(const int64_t* 
     }
 }
 
-// the probes' bucket partition as packed records (bucket << 32 | probe) for the onesweep
-// sort, and back to the two arrays the consumers read
-__global__ __launch_bounds__(kBlock) void bucket_rec_kernel(const uint32_t* __restrict__ b, uint64_t P,
-                                                            uint64_t* __restrict__ rec) {
-    const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (k < P) rec[k] = ((uint64_t)b[k] << 32) | k;
-}
-
-__global__ __launch_bounds__(kBlock) void bucket_split_kernel(const uint64_t* __restrict__ rec, uint64_t P,
-                                                              uint32_t* __restrict__ b, uint32_t* __restrict__ ids) {
-    const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (k >= P) return;
-    const uint64_t r = rec[k];
-    b[k] = (uint32_t)(r >> 32);
-    ids[k] = (uint32_t)r;
-}
-
 // ---- sharded FindMatches: chains labelled where the probes are (mums_shard_chain_*) -----
 // cdest[c] = destination rank of chain c = the rank owning its first probe's bucket (all
 // probes of a chain share one line, hence one offset and one bucket, MemHash.cpp:213)
@@ -786,19 +769,6 @@ hipError_t launch_entry_first(const uint32_t* scdest, uint64_t nch, const uint32
     return hipGetLastError();
 }
 
-hipError_t launch_bucket_records(const uint32_t* b, uint64_t P, uint64_t* rec, hipStream_t st) {
-    if (P == 0) return hipSuccess;
-    hipLaunchKernelGGL(bucket_rec_kernel, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, b, P, rec);
-    return hipGetLastError();
-}
-
-hipError_t launch_bucket_split(const uint64_t* rec, uint64_t P, uint32_t* b, uint32_t* ids, hipStream_t st) {
-    if (P == 0) return hipSuccess;
-    hipLaunchKernelGGL(bucket_split_kernel, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rec, P, b,
-                       ids);
-    return hipGetLastError();
-}
-
 uint64_t group_slot_count(uint64_t ntiles) { return ntiles * kSlots; }
 uint64_t group_blocks(uint64_t ntiles, bool packed) { return packed ? ntiles * kGSplit : ntiles; }
 
@@ -850,7 +820,7 @@ hipError_t launch_probe_tiles(View v, const SegTile* tiles, uint64_t ntiles, uin
     if constexpr (RecIB<View>::value > 0) {
         const bool fast = mp.repeat_tol == 0 && mp.enum_tol == 1;
         const double inv_t = 1.0 / (double)mp.table_size;
-        if (RecIB<View>::value == 32 && gt.gl_n > 0 && fast && !getenv("MUMS_DEV_PROBE_GENERAL"))
+        if (RecIB<View>::value == 32 && gt.gl_n > 0 && fast)
             hipLaunchKernelGGL((probe_tile_rec_kernel<MG, RecIB<View>::value, true, true>),
                                dim3((unsigned)(ntiles * kGSplit)), dim3(kBlock), 0, st, v.rec, tiles, gt, mp, L,
                                tile_count, slot_info, slot_bucket, (DevCounters*)counters, inv_t);

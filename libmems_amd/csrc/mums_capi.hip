@@ -134,7 +134,6 @@ struct mums_ctx {
     uint32_t nchunks = 0;
     DevBuf cval, ctab;
     DevBuf fsk;              // FindMatches: first-genome start of each probe (key order)
-    DevBuf bst2;             // {0, P}: the one bucket of the probes' onesweep bucket sort
     bool fused_keys = false; // materialize_seeds also writes the line keys and fsk (find_tail)
     bool rows_narrow = false; // ctx->mprobe holds int32 rows (MatProbes::rows32; materialize_dispatch)
     // one genome's SML / seed frequencies (sml_tools.hip) and filtered MatchLists
@@ -1069,7 +1068,6 @@ int merge_stage(mums_ctx* ctx, uint64_t n, int mb, int key_bits, const MatchPara
 // by hash bucket (stable: key order kept inside a bucket; values = probe ids) (A10).
 // find_follows: FindMatches runs next on this context; its one-pass replay (launch_replay_kept)
 // orders only the kept probes by bucket, so the bucket order of all probes is skipped there
-// (MUMS_DEV_KEEP_BUCKET_ORDER, read per call: sort them anyway)
 int finish_seeds(mums_ctx* ctx, const ProbeSpace& ps, hipStream_t st, bool find_follows = false) {
     DevCounters* dc = ctx->counters.as<DevCounters>();
     HIPCHK(hipMemcpyAsync(&ctx->hc, dc, sizeof(DevCounters), hipMemcpyDeviceToHost, st));
@@ -1083,38 +1081,19 @@ int finish_seeds(mums_ctx* ctx, const ProbeSpace& ps, hipStream_t st, bool find_
     int tbits = 1;
     while (tbits < 32 && ((uint64_t)1 << tbits) < (uint64_t)ctx->table_size) ++tbits;
     const uint64_t P = ctx->P;
-    if (find_follows && P > 0 && P <= find_chunk() && !ctx->shard && !getenv("MUMS_DEV_KEEP_BUCKET_ORDER")) {
+    if (find_follows && P > 0 && P <= find_chunk() && !ctx->shard) {
         ctx->sorted_buckets = nullptr;
         ctx->sorted_ids = nullptr;
         HIPCHK(hipEventRecord(ctx->ev[EV_BUCKETS], st));
         return MUMS_OK;
     }
-    // the onesweep variant (MUMS_DEV_BUCKET_ONESWEEP) moves packed 8-B records: 2.36 vs 1.56 ms
-    // on C3's 1e8 probes (u32 keys and ids in the radix passes move fewer bytes)
-    const bool radix = getenv("MUMS_DEV_BUCKET_ONESWEEP") == nullptr;
-    // (the seed sort's scratch holds the onesweep workspace: ctx->tmp is not regrown here, other
-    // stages may hold pointers into it)
-    if (!radix && P >= 4096 && P < (1ull << 30) && ps.slot_info + P <= (const uint64_t*)ps.probe_bucket &&
-        ctx->tmp.cap >= onesweep_tmp_bytes(P, 0, tbits)) {
-        // one onesweep sort of packed (bucket << 32 | probe) records: the dead slot array and
-        // [bucketB, idsA] are the ping-pong pair, the sorted partition lands in probe_bucket / idsB
-        uint64_t* rA = ps.slot_info;
-        uint64_t* rB = (uint64_t*)ps.bucketB;
-        HIPCHK(ctx->bst2.ensure(64));
-        HIPCHK(launch_bucket_records(ps.probe_bucket, P, rA, st));
-        HIPCHK(seg_bucket_starts(nullptr, 0, 0, P, ctx->bst2.as<uint32_t>(), st));
-        int ob = 0;
-        HIPCHK(seg_onesweep_sort(rA, rB, P, tbits, 0, ctx->bst2.as<uint32_t>(), ctx->tmp.p, &dc->err, &ob, st));
-        HIPCHK(launch_bucket_split(ob ? rB : rA, P, ps.probe_bucket, ps.idsB, st));
-        ctx->sorted_buckets = ps.probe_bucket;
-        ctx->sorted_ids = ps.idsB;
-    } else {
-        int pout = 0;
-        HIPCHK(radix_sort<uint32_t>(ps.probe_bucket, nullptr, P, tbits, ps.bucketB, ps.idsA, ps.probe_bucket,
-                                    ps.idsB, ctx->tmp.p, &pout, st));
-        ctx->sorted_buckets = pout ? ps.probe_bucket : ps.bucketB;
-        ctx->sorted_ids = pout ? ps.idsB : ps.idsA;
-    }
+    // u32 keys and ids in 8-bit radix passes: 1.56 ms on C3's 1e8 probes (one onesweep sort of
+    // packed 8-B records moved more bytes: 2.36 ms)
+    int pout = 0;
+    HIPCHK(radix_sort<uint32_t>(ps.probe_bucket, nullptr, P, tbits, ps.bucketB, ps.idsA, ps.probe_bucket, ps.idsB,
+                                ctx->tmp.p, &pout, st));
+    ctx->sorted_buckets = pout ? ps.probe_bucket : ps.bucketB;
+    ctx->sorted_ids = pout ? ps.idsB : ps.idsA;
     HIPCHK(hipEventRecord(ctx->ev[EV_BUCKETS], st));
     return MUMS_OK;
 }
@@ -1439,8 +1418,6 @@ int run_pipeline(mums_ctx* ctx, int stage) {
     const int kbits = 2 * ctx->w + 1;
     ctx->packed_path = kbits <= 32 + kMaxMsdBits;
     ctx->msd_bits = ctx->packed_path ? std::max(0, kbits - 32) : 0;
-    if (const char* e = getenv("MUMS_DEV_MSD_BITS"))   // development knob (sort layout experiments)
-        if (ctx->packed_path) ctx->msd_bits = std::min(kMaxMsdBits, std::max(ctx->msd_bits, atoi(e)));
     // the three-pass sort (MUMS_DEV_SORT3) sorts 30 bits: the 8-bit MSD scatter leaves 31 key
     // bits in a w19 record, the parity bit stays unsorted (default tolerances only)
     if (ctx->packed_path && seg_wide_sort_enabled() && ctx->msd_bits < 8 && kbits - 8 <= 31 && kbits > 8 &&
@@ -1449,8 +1426,7 @@ int run_pipeline(mums_ctx* ctx, int stage) {
     const int B = ctx->msd_bits;
     // keys wider than 32 + 8 bits: an 8-bit scatter + side bytes + msd_split (msdsplit.hip)
     // instead of a 2^B-digit scatter (write runs of ~2 records per tile at w21)
-    const int side = (ctx->packed_path && B > 8 && !getenv("MUMS_DEV_MSD_BITS") && !getenv("MUMS_DEV_NO_SPLIT"))
-                         ? B - 8 : 0;
+    const int side = (ctx->packed_path && B > 8 && !getenv("MUMS_DEV_NO_SPLIT")) ? B - 8 : 0;
     const size_t kb = ctx->key64 ? 8 : 4;
     ProbeSpace ps{};
     if (ctx->packed_path) {
@@ -2268,7 +2244,7 @@ int mums_ctx_destroy(mums_ctx* ctx) {
                       &ctx->smlvB, &ctx->smltmp, &ctx->flen, &ctx->fs, &ctx->rowsall, &ctx->rsbuf,
                       &ctx->rsplan, &ctx->rsbst, &ctx->pool_loc, &ctx->cbuf, &ctx->sids,
                       &ctx->logA, &ctx->logB, &ctx->logvA, &ctx->logvB, &ctx->tiebuf, &ctx->fk, &ctx->fkloc,
-                      &ctx->crbuf, &ctx->crcnt, &ctx->crlive, &ctx->crruns, &ctx->crall, &ctx->fsk, &ctx->bst2,
+                      &ctx->crbuf, &ctx->crcnt, &ctx->crlive, &ctx->crruns, &ctx->crall, &ctx->fsk,
                       &ctx->side, &ctx->bst8, &ctx->cbst, &ctx->dsarr, &ctx->labx, &ctx->rkpool0, &ctx->rkpool1,
                       &ctx->rku32, &ctx->ascii_all, &ctx->keep_pool, &ctx->keep_cnt, &ctx->bt_ascii, &ctx->bt_seg,
                       &ctx->bt_keys, &ctx->bt_kA, &ctx->bt_kB, &ctx->bt_vA, &ctx->bt_vB, &ctx->bt_tmp, &ctx->bt_ord,

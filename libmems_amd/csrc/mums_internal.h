@@ -320,8 +320,6 @@ hipError_t launch_probe_compact(uint64_t nblocks, const uint32_t* tile_count, co
                                 const uint64_t* slot_info, const uint32_t* slot_bucket, uint64_t* probe_info,
                                 uint32_t* probe_bucket, hipStream_t st, bool packed);
 // the bucket partition of the probes as packed records (bucket << 32 | probe) and back
-hipError_t launch_bucket_records(const uint32_t* b, uint64_t P, uint64_t* rec, hipStream_t st);
-hipError_t launch_bucket_split(const uint64_t* rec, uint64_t P, uint32_t* b, uint32_t* ids, hipStream_t st);
 // probes (key order) -> materialized rows (MatProbes, match_device.h)
 template <int MG, typename View>
 // lkey / fsk (optional): each probe's line key (chain_lkey_slot) and first-genome start;

@@ -29,54 +29,14 @@ constexpr int kTile = kSegTile;
 constexpr int kRounds = kTile / kBlock;  // 16
 constexpr int kWaves = kBlock / 64;
 constexpr int kDigits = 256;
-#ifndef MUMS_SORT_BLOCK
-#define MUMS_SORT_BLOCK 768
-#endif
-#ifndef MUMS_SORT_TILE
-#define MUMS_SORT_TILE 9216
-#endif
-#ifndef MUMS_SORT_NT
-#define MUMS_SORT_NT 0      // bit 0: non-temporal record loads, bit 1: non-temporal stores
-#endif
-#ifndef MUMS_SORT_PERSIST
-#define MUMS_SORT_PERSIST 0
-#endif
-constexpr int kSortBlock = MUMS_SORT_BLOCK;    // threads per onesweep block
-constexpr int kSortTile = MUMS_SORT_TILE;      // records per onesweep tile (longer digit runs per store)
-#ifndef MUMS_OS_LATEPUB
-#define MUMS_OS_LATEPUB 0   // 1: publish the tile aggregate after ranking (no early per-digit atomics)
-#endif
-#ifndef MUMS_OS_NEXTHIST
-#define MUMS_OS_NEXTHIST 0  // 1: pass p counts the pass-(p+1) digits (the histogram read covers digit 0 only)
-#endif
-#ifndef MUMS_OS_FUSED
-#define MUMS_OS_FUSED 1     // 1: fold lstart into the per-wave bases and the output offsets (one LDS
-                            // read per record in each scatter, and no digit kept per record: <= 80 VGPRs)
-#endif
+// The onesweep block shape: 768 threads x 12 records (9216-record tiles: 74 KB of LDS, two
+// blocks and 24 waves per CU).  Smaller tiles (more blocks per CU) measured 2.5-14 % slower per
+// pass: the digit runs a tile stores get shorter.
+constexpr int kSortBlock = 768;     // threads per onesweep block
+constexpr int kSortTile = 9216;     // records per onesweep tile
 #ifndef MUMS_LOOKBACK
 #define MUMS_LOOKBACK 4
 #endif
-#ifndef MUMS_OS_CTILES
-#define MUMS_OS_CTILES 0    // 1: descriptors copied into claim order (one load per claim): measured 1.3 % slower per pass
-#endif
-
-#ifndef MUMS_OS_STATS
-#define MUMS_OS_STATS 0     // 1 (development build): per-phase wall-clock sums of the onesweep blocks
-#endif
-#if MUMS_OS_STATS
-// per claimed tile: 8 s_memrealtime stamps (100 MHz) of its block's phases, then the block id
-// (plain stores: the host reduces them after every pass)
-__device__ unsigned long long* g_os_stats;
-#define OS_STAMP(k)                                                                  \
-    do {                                                                             \
-        if (tid == 0) ts[k] = __builtin_amdgcn_s_memrealtime();                      \
-    } while (0)
-#else
-#define OS_STAMP(k) \
-    do {            \
-    } while (0)
-#endif
-
 constexpr int kLookback = MUMS_LOOKBACK;       // predecessor statuses fetched per look-back step
 inline uint64_t ub_status(uint64_t ub, int npass) { return ub * kDigits * (uint64_t)npass; }
 
@@ -171,19 +131,7 @@ __global__ __launch_bounds__(256) void claim_order_kernel(const uint32_t* __rest
     tiles[pos].order = (uint32_t)t;
 }
 
-// ctiles[c] = the descriptor of the c-th claimed tile (ctiles[c].order = its tile index): a
-// claiming block then reads its tile with one load after the claim
-__global__ __launch_bounds__(256) void claim_tiles_kernel(const SegTile* __restrict__ tiles, uint64_t ub,
-                                                          SegTile* __restrict__ ctiles) {
-    const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ub) return;
-    const uint32_t t = tiles[c].order;
-    SegTile d = tiles[t];
-    d.order = t;
-    ctiles[c] = d;
-}
-
-// XCD-grouped claim queues (default; MUMS_DEV_OS_XCD=0 turns them off): bucket b's tiles form queue
+// XCD-grouped claim queues (sorts of >= 8 MSD buckets): bucket b's tiles form queue
 // b % 8, in (tile-in-bucket, bucket) order inside the queue; blocks b and b + 8 share an XCD
 // (round-robin dispatch, MI355X_MICROARCH.md: a speed-only affinity), so a block claims from
 // queue blockIdx % 8 first: consecutive tiles of a bucket -- whose digit runs abut in the
@@ -423,10 +371,9 @@ __global__ __launch_bounds__(kBlock) void seg_ghist_kernel(const uint64_t* __res
 // one block per (bucket, pass): dbase = bstart[b] + exclusive scan over digits
 __global__ __launch_bounds__(kBlock) void seg_dbase_kernel(const uint32_t* __restrict__ ghist,
                                                            const uint32_t* __restrict__ bstart, int npass,
-                                                           uint32_t* __restrict__ dbase, int pass) {
+                                                           uint32_t* __restrict__ dbase) {
     __shared__ uint32_t s_w[kWaves];
-    // pass < 0: one block per (bucket, pass); else one block per bucket for that pass
-    const uint64_t bp = pass < 0 ? (uint64_t)blockIdx.x : (uint64_t)blockIdx.x * npass + pass;
+    const uint64_t bp = blockIdx.x;
     const uint32_t b = (uint32_t)(bp / npass);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t v = ghist[bp * kDigits + threadIdx.x];
@@ -458,13 +405,14 @@ __device__ __forceinline__ void onesweep_load(const uint64_t* __restrict__ rin, 
 // order = tiles[c].order, see claim_order_kernel), so every tile it waits on was
 // claimed earlier by a resident block.  OB threads x kIPT records per tile; the first
 // 256 threads also own one digit each for the look-back and the digit starts.
-// kAlias: the per-wave digit counts live in the record exchange buffer (every lane folds
-// its slot base into its ranks before the exchange), so a tile costs kT * 8 B + 4 KB of LDS.
+// The per-wave digit counts live in the record exchange buffer (every lane folds its slot
+// base into its ranks before the exchange), so a tile costs kT * 8 B + 4 KB of LDS.
+// kLate: the tile aggregate is published after the ranking (no early per-digit atomics)
 // kGath (the line sort's last pass): instead of record k, gout[o] = low 32 bits of
 // gsrc[low 32 bits of k] -- the permutation gather of the caller, done at the store
 // kHi (the host sets it when shift >= 32): the pass's digit lies in the record's high word
 // Two blocks of the default shape (768 threads) per CU need six waves per SIMD, i.e. <= 80 VGPRs.
-template <int OB, int kIPT, bool kAlias = false, bool kLate = false, bool kGath = false, bool kHi = false>
+template <int OB, int kIPT, bool kLate = false, bool kGath = false, bool kHi = false>
 __global__ __launch_bounds__(OB) __attribute__((amdgpu_waves_per_eu(OB == 768 ? 6 : 1)))
 void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
                                                           uint64_t* __restrict__ rout,
@@ -472,32 +420,23 @@ void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
                                                           int shift, int pass, int npass,
                                                           const uint32_t* __restrict__ dbase, uint32_t* status,
                                                           uint32_t* tile_counter, uint32_t* err,
-                                                          uint32_t* __restrict__ ghist_next,
                                                           const uint32_t* __restrict__ xq,
                                                           const uint64_t* __restrict__ gsrc = nullptr,
                                                           uint32_t* __restrict__ gout = nullptr,
                                                           const uint4* __restrict__ xd = nullptr) {
     constexpr int kT = kIPT * OB;
-    constexpr bool late = MUMS_OS_LATEPUB || kLate;
     constexpr int kW = OB / 64;
     static_assert(OB >= kDigits, "one thread per digit");
-    static_assert(!kAlias || kW * kDigits * 4 <= kT * 8, "counts fit in the exchange buffer");
+    static_assert(kW * kDigits * 4 <= kT * 8, "counts fit in the exchange buffer");
     __shared__ uint64_t srec[kT];
-    __shared__ uint32_t wcnt_own[kAlias ? 1 : kW][kDigits];
-    uint32_t (*wcnt)[kDigits] = kAlias ? reinterpret_cast<uint32_t (*)[kDigits]>(srec) : wcnt_own;
-    __shared__ uint32_t lstart[kDigits];
+    uint32_t (*wcnt)[kDigits] = reinterpret_cast<uint32_t (*)[kDigits]>(srec);
     __shared__ uint32_t gofs[kDigits];
     __shared__ uint32_t s_w[kDigits / 64];
     __shared__ uint32_t s_tile;
     __shared__ uint32_t hcnt[kDigits];
-    __shared__ uint32_t hnext[kDigits];   // next pass's digit counts (ghist_next != null)
     __shared__ uint4 s_desc;              // the claimed tile's descriptor (xd)
     __shared__ uint32_t s_far;            // an output offset of this tile may pass 2^32 bytes
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#if MUMS_OS_STATS
-    unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    OS_STAMP(0);
     if (tid == 0) {
         if (xq) {   // XCD-grouped queues (xcd_order_kernel): s_tile = the tile itself
             uint32_t tt = 0xFFFFFFFFu;
@@ -523,15 +462,11 @@ void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
         }
     }
     for (int i = tid; i < kW * kDigits; i += OB) (&wcnt[0][0])[i] = 0;
-    if (tid < kDigits) { hcnt[tid] = 0; hnext[tid] = 0; }
+    if (tid < kDigits) hcnt[tid] = 0;
     if (tid == 0) s_far = 0;
     __syncthreads();
     const uint32_t c = __builtin_amdgcn_readfirstlane(s_tile);   // uniform: scalar descriptor loads
     if (xq ? c == 0xFFFFFFFFu : c >= nclaims) return;
-#if MUMS_OS_CTILES
-    const SegTile d = tiles[c];   // claim-ordered copy (claim_tiles_kernel)
-    const uint32_t t = __builtin_amdgcn_readfirstlane(d.order);
-#else
     const uint32_t t = xq ? c : __builtin_amdgcn_readfirstlane(tiles[c].order);
     SegTile d{};
     if (xd) {   // uniform: the descriptor the claim loaded
@@ -543,19 +478,13 @@ void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
     } else {
         d = tiles[t];
     }
-#endif
     if (d.count == 0) return;
-    OS_STAMP(1);
     const uint32_t q0 = wv * (kT / kW);
     auto qof = [&](int r) -> uint32_t { return q0 + (uint32_t)r * 64u + (uint32_t)lane; };
     // the pass's digit of a record: a 32-bit field of the high word when it lies there (kHi)
     auto digit = [&](uint64_t k) -> uint32_t {
         if constexpr (kHi) return ((uint32_t)(k >> 32) >> (shift - 32)) & 0xFFu;
         else return (uint32_t)(k >> shift) & 0xFFu;
-    };
-    auto digit_next = [&](uint64_t k) -> uint32_t {
-        if constexpr (kHi) return ((uint32_t)(k >> 32) >> (shift - 24)) & 0xFFu;
-        else return (uint32_t)(k >> (shift + 8)) & 0xFFu;
     };
     // the bucket's first output record (the exclusive digit scan starts there): the stores
     // address it plus a 32-bit byte offset when every offset of this tile fits
@@ -578,16 +507,12 @@ void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
         for (int r = 0; r < kIPT; ++r) {
             const uint32_t q = qof(r);
             const bool in = decltype(full_c)::value || q < d.count;
-#if MUMS_SORT_NT & 1
-            key[r] = in ? __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(tin + q * 8u)) : ~0ull;   // read once per pass
-#else
             key[r] = in ? *reinterpret_cast<const uint64_t*>(tin + q * 8u) : ~0ull;
-#endif
         }
     };
     if (full) loads(std::true_type{});
     else loads(std::false_type{});
-    if constexpr (!late) {
+    if constexpr (!kLate) {
         // publish this tile's per-digit counts as soon as the keys are in: successors'
         // look-backs then rarely find an unpublished predecessor.  (Late: after the ranking,
         // from its per-wave counts -- for keys in runs of equal digits, whose per-record LDS
@@ -596,16 +521,10 @@ void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
         for (int r = 0; r < kIPT; ++r)
             atomicAdd(&hcnt[digit(key[r])], 1u);
         __syncthreads();
-        OS_STAMP(2);
         if (d.tb != 0 && tid < kDigits)
             __hip_atomic_store(status + (uint64_t)t * kDigits + tid,
                                kFlagAgg | (hcnt[tid] - (tid == kDigits - 1 ? pad : 0u)), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (ghist_next) {   // uniform: the next pass's histogram rides on this pass's read
-        #pragma unroll
-        for (int r = 0; r < kIPT; ++r)
-            atomicAdd(&hnext[digit_next(key[r])], 1u);
     }
     #pragma unroll
     for (int r = 0; r < kIPT; ++r) {
@@ -616,7 +535,6 @@ void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
         rank[r] = old + rk;
     }
     __syncthreads();
-    OS_STAMP(3);
     uint32_t v = 0, acc = 0;
     if (tid < kDigits) {
         const int dgt = tid;  // digit
@@ -625,7 +543,7 @@ void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
         if (dgt == kDigits - 1) acc -= pad;
         // look back over the bucket's preceding tiles, then publish the inclusive prefix
         uint32_t* st = status + (uint64_t)t * kDigits + dgt;
-        if (late && d.tb != 0) __hip_atomic_store(st, kFlagAgg | acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (kLate && d.tb != 0) __hip_atomic_store(st, kFlagAgg | acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         uint32_t prefix = 0;
         if (d.tb == 0) {
             __hip_atomic_store(st, kFlagInc | acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -679,46 +597,25 @@ void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
         if (lane == 63) s_w[wv] = v;
     }
     __syncthreads();
-    OS_STAMP(4);
     if (tid < kDigits) {
         uint32_t wpre = 0;
         #pragma unroll
         for (int w = 0; w < kDigits / 64; ++w) wpre += (w < wv) ? s_w[w] : 0u;
-        lstart[tid] = wpre + v - acc;
-#if MUMS_OS_FUSED
         // one LDS read per record in each scatter: per-wave LDS slot base and the
         // tile-slot -> output offset of every digit
         const uint32_t ls = wpre + v - acc;
         #pragma unroll
         for (int w = 0; w < kW; ++w) wcnt[w][tid] += ls;
         gofs[tid] -= ls;
-#endif
     }
     __syncthreads();
-    if constexpr (kAlias) {   // slots first: the exchange overwrites the counts
-        #pragma unroll
-        for (int r = 0; r < kIPT; ++r) {
-#if MUMS_OS_FUSED
-            rank[r] += wcnt[wv][digit(key[r])];
-#else
-            rank[r] += lstart[digit(key[r])] + wcnt[wv][digit(key[r])];
-#endif
-        }
-        __syncthreads();
-        #pragma unroll
-        for (int r = 0; r < kIPT; ++r) srec[rank[r]] = key[r];
-    } else {
+    // slots first: the exchange overwrites the counts
     #pragma unroll
-    for (int r = 0; r < kIPT; ++r) {
-#if MUMS_OS_FUSED
-        srec[wcnt[wv][digit(key[r])] + rank[r]] = key[r];
-#else
-        srec[lstart[digit(key[r])] + wcnt[wv][digit(key[r])] + rank[r]] = key[r];
-#endif
-    }
-    }
+    for (int r = 0; r < kIPT; ++r) rank[r] += wcnt[wv][digit(key[r])];
     __syncthreads();
-    OS_STAMP(5);
+    #pragma unroll
+    for (int r = 0; r < kIPT; ++r) srec[rank[r]] = key[r];
+    __syncthreads();
     uint64_t* bout = rout + bb;
     uint32_t* bgout = kGath ? gout + bb : nullptr;
     // far: some offset of this tile, in bytes, may not fit 32 bits (a bucket above 4 GB)
@@ -730,11 +627,7 @@ void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
             if (decltype(full_c)::value || sidx < d.count) {
                 const uint64_t k = srec[sidx];
                 const uint32_t sd = digit(k);
-#if MUMS_OS_FUSED
-                const uint32_t o = gofs[sd] + sidx;   // gofs holds out offset - lstart (mod 2^32)
-#else
-                const uint32_t o = gofs[sd] + (sidx - lstart[sd]);
-#endif
+                const uint32_t o = gofs[sd] + sidx;   // gofs holds out offset - digit start in LDS (mod 2^32)
                 if constexpr (kGath) {
                     const uint32_t gv = (uint32_t)gsrc[(uint32_t)k];
                     if constexpr (kFar) bgout[o] = gv;
@@ -742,11 +635,7 @@ void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
                 } else {
                     uint64_t* op = kFar ? bout + o
                                         : reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(bout) + o * 8u);
-#if MUMS_SORT_NT & 2
-                    __builtin_nontemporal_store(k, op);
-#else
                     *op = k;
-#endif
                 }
             }
         }
@@ -754,190 +643,6 @@ void seg_onesweep_kernel(const uint64_t* __restrict__ rin,
     if (s_far) stores(std::false_type{}, std::true_type{});
     else if (full) stores(std::true_type{}, std::false_type{});
     else stores(std::false_type{}, std::false_type{});
-    if (ghist_next && tid < kDigits) {   // hnext complete: barriers since its atomics
-        const uint32_t c = hnext[tid] - (tid == kDigits - 1 ? pad : 0u);
-        if (c) atomicAdd(&ghist_next[((uint64_t)d.bucket * npass + pass + 1) * kDigits + tid], c);
-    }
-#if MUMS_OS_STATS
-    OS_STAMP(6);
-    __builtin_amdgcn_s_waitcnt(0);   // this wave's stores retired
-    OS_STAMP(7);
-    if (tid == 0) {
-        unsigned long long* o = g_os_stats + (uint64_t)t * 10;
-        for (int k = 0; k < 8; ++k) o[k] = ts[k];
-        o[8] = blockIdx.x;
-        o[9] = 1;
-    }
-#endif
-}
-
-// Persistent onesweep pass: a resident grid of blocks, each claiming tiles in claim
-// order from the counter until none is left.  The next tile's records are loaded
-// right after the current tile's look-back, so their HBM latency overlaps the current
-// tile's LDS reorder and stores.  A block holds at most its current tile and the one
-// after it; the earliest unfinished claim is always a current tile whose predecessors
-// are all finished, so the look-back chain always progresses.
-template <int OB, int kIPT>
-__global__ __launch_bounds__(OB) __attribute__((amdgpu_waves_per_eu(4))) void seg_onesweep_persist_kernel(const uint64_t* __restrict__ rin,
-                                                                  uint64_t* __restrict__ rout,
-                                                                  const SegTile* __restrict__ tiles,
-                                                                  uint32_t nclaims, int shift, int pass, int npass,
-                                                                  const uint32_t* __restrict__ dbase,
-                                                                  uint32_t* status, uint32_t* tile_counter,
-                                                                  uint32_t* err) {
-    constexpr int kT = kIPT * OB;
-    constexpr int kW = OB / 64;
-    static_assert(OB >= kDigits, "one thread per digit");
-    __shared__ uint64_t srec[kT];
-    __shared__ uint32_t wcnt[kW][kDigits];
-    __shared__ uint32_t lstart[kDigits];
-    __shared__ uint32_t gofs[kDigits];
-    __shared__ uint32_t s_w[kDigits / 64];
-    __shared__ uint32_t s_tile[2];
-    __shared__ uint32_t hcnt[kDigits];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const uint32_t q0 = wv * (kT / kW);
-    if (tid == 0) s_tile[0] = atomicAdd(tile_counter, 1u);
-    __syncthreads();
-    uint32_t c = __builtin_amdgcn_readfirstlane(s_tile[0]);
-    uint64_t key[kIPT];
-    uint32_t rank[kIPT];
-    SegTile d{};
-    uint32_t t = 0;
-    if (c < nclaims) {
-        t = __builtin_amdgcn_readfirstlane(tiles[c].order);
-        d = tiles[t];
-        #pragma unroll
-        for (int r = 0; r < kIPT; ++r) {
-            const uint32_t q = q0 + r * 64 + lane;
-            key[r] = q < d.count ? rin[d.start + q] : 0ull;
-        }
-    }
-    int par = 0;
-    while (c < nclaims) {
-        // claim the next tile now (its id is needed before the prefetch below)
-        if (tid == 0) s_tile[par ^ 1] = atomicAdd(tile_counter, 1u);
-        for (int i = tid; i < kW * kDigits; i += OB) (&wcnt[0][0])[i] = 0;
-        if (tid < kDigits) hcnt[tid] = 0;
-        __syncthreads();
-        const uint32_t cn = __builtin_amdgcn_readfirstlane(s_tile[par ^ 1]);
-        #pragma unroll
-        for (int r = 0; r < kIPT; ++r) {
-            const uint32_t q = q0 + r * 64 + lane;
-            if (q < d.count) atomicAdd(&hcnt[(uint32_t)(key[r] >> shift) & 0xFFu], 1u);
-        }
-        __syncthreads();
-        if (d.tb != 0 && tid < kDigits)
-            __hip_atomic_store(status + (uint64_t)t * kDigits + tid, kFlagAgg | hcnt[tid], __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        #pragma unroll
-        for (int r = 0; r < kIPT; ++r) {
-            const uint32_t q = q0 + r * 64 + lane;
-            const bool valid = q < d.count;
-            const uint32_t dg = (uint32_t)(key[r] >> shift) & 0xFFu;
-            uint32_t tot;
-            const uint32_t rk = wave_match_rank<8>(dg, valid, &tot);
-            uint32_t old = 0;
-            if (valid) old = wcnt[wv][dg];
-            if (valid && rk == 0) wcnt[wv][dg] = old + tot;
-            rank[r] = old + rk;
-        }
-        __syncthreads();
-        uint32_t v = 0, acc = 0;
-        if (tid < kDigits) {
-            const int dg = tid;
-            #pragma unroll
-            for (int w = 0; w < kW; ++w) { const uint32_t x = wcnt[w][dg]; wcnt[w][dg] = acc; acc += x; }
-            uint32_t* st = status + (uint64_t)t * kDigits + dg;
-            uint32_t prefix = 0;
-            if (d.tb == 0) {
-                __hip_atomic_store(st, kFlagInc | acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                const int64_t tfirst = (int64_t)t - (int64_t)d.tb;
-                int64_t j = (int64_t)t - 1;
-                uint32_t spins = 0;
-                bool done = false;
-                while (!done) {
-                    uint32_t sv[kLookback];
-                    #pragma unroll
-                    for (int k = 0; k < kLookback; ++k)
-                        sv[k] = (j - k >= tfirst) ? __hip_atomic_load(status + (uint64_t)(j - k) * kDigits + dg,
-                                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                                  : kFlagInc;
-                    int used = 0;
-                    bool stall = false;
-                    #pragma unroll
-                    for (int k = 0; k < kLookback; ++k) {
-                        if (done || stall) continue;
-                        const uint32_t sx = sv[k];
-                        if ((sx >> 30) == 0u) { stall = true; continue; }
-                        prefix += sx & kValMask;
-                        ++used;
-                        if ((sx & kFlagInc) != 0u) done = true;
-                    }
-                    j -= used;
-                    if (stall && !done) {
-                        if (++spins > (1u << 24)) { atomicOr(err, 2u); break; }
-                        if (spins < 8) __builtin_amdgcn_s_sleep(1);
-                        else __builtin_amdgcn_s_sleep(8);
-                    }
-                }
-                __hip_atomic_store(st, kFlagInc | ((prefix + acc) & kValMask), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            }
-            gofs[dg] = dbase[((uint64_t)d.bucket * npass + pass) * kDigits + dg] + prefix;
-            v = acc;
-            #pragma unroll
-            for (int dd = 1; dd < 64; dd <<= 1) {
-                const uint32_t x = __shfl_up(v, dd, 64);
-                if (lane >= dd) v += x;
-            }
-            if (lane == 63) s_w[wv] = v;
-        }
-        __syncthreads();
-        if (tid < kDigits) {
-            uint32_t wpre = 0;
-            #pragma unroll
-            for (int w = 0; w < kDigits / 64; ++w) wpre += (w < wv) ? s_w[w] : 0u;
-            lstart[tid] = wpre + v - acc;
-        }
-        __syncthreads();
-        #pragma unroll
-        for (int r = 0; r < kIPT; ++r) {
-            const uint32_t q = q0 + r * 64 + lane;
-            if (q < d.count) {
-                const uint32_t dg = (uint32_t)(key[r] >> shift) & 0xFFu;
-                srec[lstart[dg] + wcnt[wv][dg] + rank[r]] = key[r];
-            }
-        }
-        // prefetch the next tile's records into the key registers (now free)
-        SegTile dn{};
-        uint32_t tn = 0;
-        if (cn < nclaims) {
-            tn = __builtin_amdgcn_readfirstlane(tiles[cn].order);
-            dn = tiles[tn];
-            #pragma unroll
-            for (int r = 0; r < kIPT; ++r) {
-                const uint32_t q = q0 + r * 64 + lane;
-                key[r] = q < dn.count ? rin[dn.start + q] : 0ull;
-            }
-        }
-        __syncthreads();
-        #pragma unroll
-        for (int r = 0; r < kIPT; ++r) {
-            const uint32_t sidx = tid + r * OB;
-            if (sidx < d.count) {
-                const uint64_t k = srec[sidx];
-                const uint32_t dg = (uint32_t)(k >> shift) & 0xFFu;
-                rout[(uint64_t)gofs[dg] + (sidx - lstart[dg])] = k;
-            }
-        }
-        __syncthreads();   // srec / gofs / lstart are rewritten by the next tile
-        c = cn;
-        d = dn;
-        t = tn;
-        par ^= 1;
-    }
 }
 
 // ---------------------------------------------------------------------------------
@@ -1113,7 +818,7 @@ __global__ __launch_bounds__(kBlock) void segfix_tile_kernel(uint64_t* rec, uint
             e = wn;                    // the stream's last segment
         }
         const int m = e - s;
-        if (m > kSfLds || (force_big == 1 && (ps & 63u) == 0u)) {   // force_big: test knob
+        if (m > kSfLds || (force_big && (ps & 63u) == 0u)) {   // force_big: test knob
             if (r == s) sf_push_big(ps, big_list, big_count, cap, err);
             continue;
         }
@@ -1125,7 +830,7 @@ __global__ __launch_bounds__(kBlock) void segfix_tile_kernel(uint64_t* rec, uint
     __syncthreads();
     // one lane per dirty segment: up to kSfReg records ranked in registers, longer ones
     // (<= kSfLds) from LDS
-    const uint32_t nj = force_big == 3 ? 0u : s_njobs;
+    const uint32_t nj = s_njobs;
     for (uint32_t j = tid; j < nj; j += kBlock) {
         const int s = (int)(jobs[j] >> 7), m = (int)(jobs[j] & 127u);
         const uint32_t ps = wbeg + (uint32_t)s;
@@ -1143,7 +848,7 @@ __global__ __launch_bounds__(kBlock) void segfix_tile_kernel(uint64_t* rec, uint
                 #pragma unroll
                 for (int u = 0; u < kSfReg; ++u)
                     rank += (d[u] < d[i] || (d[u] == d[i] && u < i)) ? 1u : 0u;
-                if (i < m && force_big != 2) rec[ps + rank] = y[i];
+                if (i < m) rec[ps + rank] = y[i];
             }
         } else {
             for (int i = 0; i < m; ++i) {
@@ -1154,7 +859,7 @@ __global__ __launch_bounds__(kBlock) void segfix_tile_kernel(uint64_t* rec, uint
                     const uint32_t du = sf_digit(w[s + u], md);
                     rank += (du < di || (du == di && u < i)) ? 1u : 0u;
                 }
-                if (force_big != 2) rec[ps + rank] = x;
+                rec[ps + rank] = x;
             }
         }
     }
@@ -1244,12 +949,12 @@ __global__ __launch_bounds__(kBlock) void segfix_big_kernel(uint64_t* rec, uint6
 // replaces costs.
 bool seg_segfix_enabled() {
     const char* e = getenv("MUMS_DEV_SEGFIX");
-    return e && (e[0] == '1' || e[0] == '2' || e[0] == '3' || e[0] == '4');
+    return e && (e[0] == '1' || e[0] == '2');
 }
 
-static int seg_segfix_force_big() {   // 1: forced big path; 2 / 3: timing experiments (results wrong)
+static int seg_segfix_force_big() {   // 1: forced big path
     const char* e = getenv("MUMS_DEV_SEGFIX");
-    return (e && e[0] == '2') ? 1 : (e && e[0] == '3') ? 2 : (e && e[0] == '4') ? 3 : 0;
+    return (e && e[0] == '2') ? 1 : 0;
 }
 
 int seg_onesweep_launches(int key_bits) {
@@ -1345,47 +1050,13 @@ static size_t seg_build_tmp_bytes(uint64_t nb) { return ((nb + 128) * 4 + scan_t
 // segments of more than kSfLds records, + the forced test entries (starts at multiples of 64)
 static uint64_t segfix_cap(uint64_t n) { return n / 32 + 2 * ((n + kSfTile - 1) / kSfTile + 2); }
 
-// development A/B of the onesweep block shape (MUMS_DEV_OS_VARIANT, read once):
-// 0 = <768 threads, 12 records> (9216-record tiles, the per-wave counts aliased into the
-// exchange buffer: 76 KB, two blocks and 24 waves per CU, 79 VGPRs), 1-6 and 8 aliased too:
-// 1 <512, 16> (8192), 2 <512, 12> and 3 <384, 16> (6144-record tiles, 52 KB: three blocks per
-// CU), 4 <256, 16> and 5 <512, 8> (4096, 36 KB: four per CU), 6 <1024, 8> (8192, 32 waves per
-// CU), 8 <640, 14> (8960); 7 = the round-2 shape <512, 16> with the counts in their own LDS
-// (8192, 78 KB).  Measured on C3 in one call: 0 is 2.5 % faster per pass than 7 and 1;
-// 6144- and 4096-record tiles (more blocks per CU) are 6-14 % slower: the digit runs a tile
-// stores get shorter.
-static int os_variant() {
-    static const int v = [] {
-        const char* e = getenv("MUMS_DEV_OS_VARIANT");
-        const int x = e ? atoi(e) : 0;
-        return x >= 0 && x <= 8 ? x : 0;
-    }();
-    return v;
-}
-// XCD-grouped claim queues (default since round 5: 3.31 -> 3.04 ms per C3 pass, same box,
-// profiles/r05j_xcd_ab.txt); MUMS_DEV_OS_XCD=0 (read per call) restores the single queue
-static bool os_xcd() {
-    const char* e = getenv("MUMS_DEV_OS_XCD");
-    return !(e && e[0] == '0');
-}
-// claim descriptors in the XCD queues (one dependent load per claim, default);
-// MUMS_DEV_OS_XD=0 (read per call) reads the tile id, then its SegTile
-static bool os_xd() {
-    const char* e = getenv("MUMS_DEV_OS_XD");
-    return !(e && e[0] == '0');
-}
-static int os_tile() {
-    static const int t[9] = {kSortTile, 8192, 6144, 6144, 4096, 4096, 8192, 8192, 8960};
-    return MUMS_SORT_PERSIST ? kSortTile : t[os_variant()];
-}
-
 size_t onesweep_tmp_bytes(uint64_t n, int msd_bits, int key_bits) {
-    const uint64_t ub = seg_tiles_upper(n, msd_bits, os_tile());
+    const uint64_t ub = seg_tiles_upper(n, msd_bits, kSortTile);
     const int npass = (key_bits + 7) / 8;
     const uint64_t nb = 1ull << msd_bits;
     const size_t b = (ub * kDigits * (uint64_t)npass + 2 * nb * npass * kDigits + 256 + 64) * 4 +
                      2 * (ub * sizeof(SegTile) + 256) + seg_build_tmp_bytes(nb) + segfix_cap(n) * 4 +
-                     256;   // + the claim-ordered copy, the fix-up's big list
+                     256;   // + the XCD claim queues (a second SegTile per tile), the fix-up's big list
     return seg_wide_sort_enabled() ? std::max(b, onesweep_wide_tmp_bytes(n, msd_bits, key_bits)) : b;
 }
 
@@ -1447,165 +1118,63 @@ hipError_t seg_onesweep_sort(uint64_t* recA, uint64_t* recB, uint64_t n, int key
     if (n == 0 || npass == 0) return hipSuccess;
     if (nkd > 4) return hipErrorInvalidValue;
     const uint64_t nb = 1ull << msd_bits;
-    const int tile = os_tile();
-    const uint64_t ub = seg_tiles_upper(n, msd_bits, tile);
+    const uint64_t ub = seg_tiles_upper(n, msd_bits, kSortTile);
     uint32_t* status = (uint32_t*)d_tmp;                       // [npass][ub][256]
     uint32_t* ghist = status + ub_status(ub, npass);           // [nb][npass][256]
     uint32_t* dbase = ghist + nb * npass * kDigits;            // [nb][npass][256]
     uint32_t* counters = dbase + nb * npass * kDigits;         // [npass] + ntiles
     const size_t zero_bytes = ((uint64_t)(counters - status) + 256) * 4;   // + the XCD queue counters
     SegTile* stiles = (SegTile*)((char*)d_tmp + ((zero_bytes + 255) & ~(size_t)255));
-    SegTile* ctiles = (SegTile*)((char*)stiles + ((ub * sizeof(SegTile) + 255) & ~(size_t)255));
-    void* btmp = (void*)((char*)ctiles + ((ub * sizeof(SegTile) + 255) & ~(size_t)255));
+    char* xqroom = (char*)stiles + ((ub * sizeof(SegTile) + 255) & ~(size_t)255);   // 48 B per tile
+    void* btmp = (void*)(xqroom + ((ub * sizeof(SegTile) + 255) & ~(size_t)255));
     hipError_t e = hipMemsetAsync(status, 0, zero_bytes, st);
     if (e != hipSuccess) return e;
-    e = build_seg_tiles_from_starts(d_bstart, msd_bits, n, stiles, counters + 32, btmp, st, tile);
+    e = build_seg_tiles_from_starts(d_bstart, msd_bits, n, stiles, counters + 32, btmp, st, kSortTile);
     if (e != hipSuccess) return e;
-#if MUMS_OS_CTILES
-    hipLaunchKernelGGL(claim_tiles_kernel, dim3((unsigned)((ub + 255) / 256)), dim3(256), 0, st, stiles, ub, ctiles);
-    const SegTile* otiles = ctiles;   // what the onesweep launches read
-    uint32_t* xq = nullptr;
-#else
-    const SegTile* otiles = stiles;
-    // XCD-grouped claim queues (development A/B): the unused claim-ordered copy's room
-    // (fewer than 8 MSD buckets: one queue is all there is)
-    uint32_t* xq = (os_xcd() && nb >= 8 && !MUMS_SORT_PERSIST) ? (uint32_t*)ctiles : nullptr;
-    // the queues' claim descriptors behind them (the claim-ordered copy's room: 48 B per tile)
-    uint4* xqd = xq ? (uint4*)(((uintptr_t)(xq + 32 + ub) + 15) & ~(uintptr_t)15) : nullptr;
-    const uint4* xd = os_xd() ? xqd : nullptr;
+    // XCD-grouped claim queues and, behind them, the queues' claim descriptors (fewer than 8
+    // MSD buckets: one queue is all there is, claimed in tiles[c].order)
+    uint32_t* xq = nb >= 8 ? (uint32_t*)xqroom : nullptr;
+    uint4* xd = xq ? (uint4*)(((uintptr_t)(xq + 32 + ub) + 15) & ~(uintptr_t)15) : nullptr;
     if (xq)
         hipLaunchKernelGGL(xcd_order_kernel, dim3((unsigned)((ub + 255) / 256)), dim3(256), 0, st,
-                           (const uint32_t*)btmp, (int)nb, ub, stiles, xq, xqd);
-#endif
+                           (const uint32_t*)btmp, (int)nb, ub, stiles, xq, xd);
     const unsigned gblocks = (unsigned)((ub + kGhistTilesPerBlock - 1) / kGhistTilesPerBlock);
-    // the histogram read counts digit 0 only when every later pass's digits are
-    // counted by the pass before it (MUMS_OS_NEXTHIST, plain onesweep kernel)
-    const bool nexthist = MUMS_OS_NEXTHIST && !MUMS_SORT_PERSIST;
-    if (hist_in && nb == 1 && !segfix && !nexthist) {   // the producer counted every pass's digits
+    if (hist_in && nb == 1 && !segfix) {   // the producer counted every pass's digits
         e = hipMemcpyAsync(ghist, hist_in, (size_t)npass * kDigits * 4, hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) return e;
     } else {
         hipLaunchKernelGGL(seg_ghist_kernel, dim3(gblocks), dim3(kBlock), 0, st, recA, stiles, ub, npass, ghist,
-                           key_shift, nexthist ? 1 : npass, key_runs ? 1 : 0);
+                           key_shift, npass, key_runs ? 1 : 0);
     }
-    if (nexthist)
-        hipLaunchKernelGGL(seg_dbase_kernel, dim3((unsigned)nb), dim3(kBlock), 0, st, ghist, d_bstart, npass, dbase,
-                           0);
-    else
-        hipLaunchKernelGGL(seg_dbase_kernel, dim3((unsigned)(nb * npass)), dim3(kBlock), 0, st, ghist, d_bstart,
-                           npass, dbase, -1);
-#if MUMS_SORT_PERSIST
-    // resident blocks of the persistent pass: occupancy x CUs of the current device
-    uint64_t persist_grid = 0;
-    {
-        int dev = 0, cus = 0, per = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per, (const void*)seg_onesweep_persist_kernel<kSortBlock, kSortTile / kSortBlock>, kSortBlock, 0);
-        persist_grid = (uint64_t)std::max(cus, 1) * (uint64_t)std::max(per, 1);
-    }
-#endif
-#if MUMS_OS_STATS
-    unsigned long long* os_dev = nullptr;   // development: the per-tile stamps of every pass
-    (void)hipMalloc(&os_dev, ub * 80);
-    (void)hipMemsetAsync(os_dev, 0, ub * 80, st);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_os_stats), &os_dev, sizeof(os_dev), 0, hipMemcpyHostToDevice);
-#endif
+    hipLaunchKernelGGL(seg_dbase_kernel, dim3((unsigned)(nb * npass)), dim3(kBlock), 0, st, ghist, d_bstart, npass,
+                       dbase);
     uint64_t* src = recA;
     uint64_t* dst = recB;
+    constexpr int kIPT = kSortTile / kSortBlock;
     for (int p = 0; p < npass; ++p) {
         if (ev_ds) (void)hipEventRecord(ev_ds[2 * p], st);
-#if MUMS_SORT_PERSIST
-        hipLaunchKernelGGL((seg_onesweep_persist_kernel<kSortBlock, kSortTile / kSortBlock>),
-                           dim3((unsigned)std::min<uint64_t>(ub, persist_grid)), dim3(kSortBlock), 0, st, src, dst,
-                           stiles, (uint32_t)ub, key_shift + 8 * p, p, npass, dbase,
-                           status + (uint64_t)p * ub * kDigits, counters + p, d_err);
-#else
-        {
-            uint32_t* gn = (nexthist && p + 1 < npass) ? ghist : (uint32_t*)nullptr;
-            uint32_t* sp = status + (uint64_t)p * ub * kDigits;
-            const int sh = key_shift + 8 * p;
-            uint32_t* tc = xq ? counters + 128 + 8 * p : counters + p;
-#define MUMS_OS_LAUNCH1(OB, IPT, AL, HI)                                                                     \
-    hipLaunchKernelGGL((seg_onesweep_kernel<OB, IPT, AL, false, false, HI>), dim3((unsigned)ub), dim3(OB), 0, st, src, \
-                       dst, otiles, (uint32_t)ub, sh, p, npass, dbase, sp, tc, d_err, gn, xq, nullptr, nullptr, xd)
-#define MUMS_OS_LAUNCH(OB, IPT, AL)                     \
-    do {                                                \
-        if (sh >= 32) MUMS_OS_LAUNCH1(OB, IPT, AL, true); \
-        else MUMS_OS_LAUNCH1(OB, IPT, AL, false);       \
-    } while (0)
-            if (key_runs && gout && p + 1 == npass) {   // the last pass stores gout[o] = gsrc[k]
-                hipLaunchKernelGGL((seg_onesweep_kernel<kSortBlock, kSortTile / kSortBlock, true, true, true>),
-                                   dim3((unsigned)ub), dim3(kSortBlock), 0, st, src, dst, otiles, (uint32_t)ub, sh, p,
-                                   npass, dbase, sp, tc, d_err, gn, xq, gsrc, gout, xd);
-            } else if (key_runs) {   // equal-digit runs: publish after the ranking (no per-record LDS atomics)
-                hipLaunchKernelGGL((seg_onesweep_kernel<kSortBlock, kSortTile / kSortBlock, true, true>),
-                                   dim3((unsigned)ub), dim3(kSortBlock), 0, st, src, dst, otiles, (uint32_t)ub, sh, p,
-                                   npass, dbase, sp, tc, d_err, gn, xq, nullptr, nullptr, xd);
-            } else
-            switch (os_variant()) {
-            case 1: MUMS_OS_LAUNCH(512, 16, true); break;
-            case 2: MUMS_OS_LAUNCH(512, 12, true); break;
-            case 3: MUMS_OS_LAUNCH(384, 16, true); break;
-            case 4: MUMS_OS_LAUNCH(256, 16, true); break;
-            case 5: MUMS_OS_LAUNCH(512, 8, true); break;
-            case 6: MUMS_OS_LAUNCH(1024, 8, true); break;
-            case 7: MUMS_OS_LAUNCH(512, 16, false); break;
-            case 8: MUMS_OS_LAUNCH(640, 14, true); break;
-            default: MUMS_OS_LAUNCH(kSortBlock, kSortTile / kSortBlock, true); break;
-            }
+        uint32_t* sp = status + (uint64_t)p * ub * kDigits;
+        const int sh = key_shift + 8 * p;
+        uint32_t* tc = xq ? counters + 128 + 8 * p : counters + p;
+#define MUMS_OS_LAUNCH(LATE, GATH, HI, GSRC, GOUT)                                                                  \
+    hipLaunchKernelGGL((seg_onesweep_kernel<kSortBlock, kIPT, LATE, GATH, HI>), dim3((unsigned)ub), dim3(kSortBlock), \
+                       0, st, src, dst, stiles, (uint32_t)ub, sh, p, npass, dbase, sp, tc, d_err, xq, GSRC, GOUT, xd)
+        if (key_runs && gout && p + 1 == npass)   // the last pass stores gout[o] = gsrc[k]
+            MUMS_OS_LAUNCH(true, true, false, gsrc, gout);
+        else if (key_runs)   // equal-digit runs: publish after the ranking (no per-record LDS atomics)
+            MUMS_OS_LAUNCH(true, false, false, nullptr, nullptr);
+        else if (sh >= 32)
+            MUMS_OS_LAUNCH(false, false, true, nullptr, nullptr);
+        else
+            MUMS_OS_LAUNCH(false, false, false, nullptr, nullptr);
 #undef MUMS_OS_LAUNCH
-#undef MUMS_OS_LAUNCH1
-        }
-#endif
         e = hipGetLastError();
         if (e != hipSuccess) return e;
-#if MUMS_OS_STATS
-        {   // development: per-phase wall clock per tile (us) of this pass; per XCD (block % 8: the
-            // real-time counters of different XCDs need not agree) the busy block slots
-            (void)hipStreamSynchronize(st);
-            std::vector<unsigned long long> hs(ub * 10);
-            (void)hipMemcpy(hs.data(), os_dev, ub * 80, hipMemcpyDeviceToHost);
-            double ph[7] = {0, 0, 0, 0, 0, 0, 0}, tot = 0;
-            unsigned long long lo[8], hi[8];
-            double busy[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int x = 0; x < 8; ++x) { lo[x] = ~0ull; hi[x] = 0; }
-            uint64_t nt = 0;
-            for (uint64_t i = 0; i < ub; ++i) {
-                const unsigned long long* o = &hs[i * 10];
-                if (!o[9]) continue;
-                ++nt;
-                for (int k = 1; k < 8; ++k) ph[k - 1] += (double)(o[k] - o[k - 1]);
-                tot += (double)(o[7] - o[0]);
-                const int x = (int)(o[8] & 7);
-                lo[x] = std::min(lo[x], o[0]);
-                hi[x] = std::max(hi[x], o[7]);
-                busy[x] += (double)(o[7] - o[0]);
-            }
-            const double d = nt ? (double)nt * 100.0 : 1.0;
-            double bs = 0, wl = 0;
-            for (int x = 0; x < 8; ++x)
-                if (hi[x] > lo[x]) { bs += busy[x] / (double)(hi[x] - lo[x]); wl = std::max(wl, (double)(hi[x] - lo[x])); }
-            fprintf(stderr, "os_stats n=%llu pass=%d tiles=%llu us/tile: claim %.2f load+count %.2f rank %.2f lookback %.2f "
-                    "lstart+exch %.2f stores %.2f drain %.2f | tile %.2f us, XCD wall %.1f us, busy block slots %.1f\n",
-                    (unsigned long long)n, p, (unsigned long long)nt, ph[0] / d, ph[1] / d, ph[2] / d, ph[3] / d,
-                    ph[4] / d, ph[5] / d, ph[6] / d, tot / d, wl / 100.0, bs);
-            (void)hipMemset(os_dev, 0, ub * 80);
-        }
-#endif
-        if (nexthist && p + 1 < npass)
-            hipLaunchKernelGGL(seg_dbase_kernel, dim3((unsigned)nb), dim3(kBlock), 0, st, ghist, d_bstart, npass,
-                               dbase, p + 1);
         if (ev_ds) (void)hipEventRecord(ev_ds[2 * p + 1], st);
         uint64_t* t = src;
         src = dst;
         dst = t;
     }
-#if MUMS_OS_STATS
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(os_dev);
-#endif
     if (segfix) {   // src holds the stream sorted above the lowest digit; dst is free scratch
         if (ev_ds) (void)hipEventRecord(ev_ds[2 * npass], st);
         SfMode md;

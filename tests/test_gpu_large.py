@@ -33,11 +33,10 @@ def md5_text(ml):
     return hashlib.md5(ml.text().encode()).hexdigest()
 
 
-@pytest.mark.parametrize("variant", [None, ("MUMS_DEV_SORT3", "3"), ("MUMS_DEV_OS_XCD", "1")],
-                         ids=["four_pass", "three_pass", "xcd_queues"])
+@pytest.mark.parametrize("variant", [None, ("MUMS_DEV_SORT3", "3")], ids=["four_pass", "three_pass"])
 def test_c3_findmatches_known_answer(gpu_lib, oracle_mod, monkeypatch, variant):
-    """variant: the three 10-bit passes with the parity bit unsorted (radix_wide.hip), or the
-    XCD-grouped claim queues of the four-pass sort."""
+    """The four-pass sort (XCD-grouped claim queues); variant: the three 10-bit passes with the
+    parity bit unsorted (radix_wide.hip)."""
     import torch
     if variant:
         monkeypatch.setenv(*variant)

@@ -2,7 +2,7 @@
 process (they are read per call, not cached): int32 rows (materialize_dispatch) vs 64-bit rows,
 the int32 rows flagged bad and rebuilt wide (the retry the genome-length guard makes
 unreachable on real inputs), the line-order rows of the sliced path (gather_line_rows, retry
-in chains.hip), the bucket sort's per-key atomics and the line sort without key runs.  Every
+in chains.hip).  Every
 variant must give the oracle's MatchList and collision count."""
 import pytest
 
@@ -15,10 +15,6 @@ VARIANTS = [
     {"MUMS_DEV_FIND_CHUNK": "40000"},
     {"MUMS_DEV_FIND_CHUNK": "40000", "MUMS_DEV_WIDE_LINE_ROWS": "1"},
     {"MUMS_DEV_FIND_CHUNK": "40000", "MUMS_DEV_WIDE_LINE_ROWS": "retry"},
-    {"MUMS_DEV_RS_NOAGG": "1"},
-    {"MUMS_DEV_LINE_NORUNS": "1"},
-    {"MUMS_DEV_LINE_GATHER": "1"},
-    {"MUMS_DEV_LINE_GATHER": "1", "MUMS_DEV_FIND_CHUNK": "40000"},
 ]
 
 

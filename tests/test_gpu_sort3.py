@@ -114,9 +114,9 @@ def test_sort3_start_points_and_repeat_tol(gpu_lib, oracle_mod, monkeypatch):
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"G{c['G']}_n{c['n']}_p{c['p']}_{c['mode']}")
 def test_xcd_claim_queues_known_answers(gpu_lib, oracle_mod, monkeypatch, case):
-    """The four-pass sort with XCD-grouped claim queues (MUMS_DEV_OS_XCD: bucket b's tiles in
-    queue b % 8, blocks claim from queue blockIdx % 8 first, then steal): same MatchList."""
-    monkeypatch.setenv("MUMS_DEV_OS_XCD", "1")
+    """The default four-pass sort, whose passes claim tiles from XCD-grouped queues (bucket b's
+    tiles in queue b % 8, blocks claim from queue blockIdx % 8 first, then steal): the known
+    MatchList."""
     seqs = oracle_mod.generate(case["G"], case["n"], case["p"], 12345)
     masked = case["mode"] == "MaskedMemHash"
     cls = gpu_lib.MaskedMemHash if masked else gpu_lib.MemHash

@@ -1,8 +1,8 @@
-"""Chain walks with refilled lanes (chain_walk_refill_kernel, MUMS_DEV_WALK_REFILL=1) against the
-one-shot short-walk kernel and the oracle.  Inputs span short walks (2 % substitutions), long
-walks that overrun the per-lane budget and go on to the lane-group kernel (0.05 %), a
+"""Chain walks (chain_walk_short_kernel, chain_walk_kernel) against the oracle, whole and with the
+probes sliced (MUMS_DEV_FIND_CHUNK).  Inputs span short walks (2 % substitutions), long walks
+that overrun the per-lane budget and go on to the lane-group kernel (0.05 %), a
 reverse-complemented genome and a non-palindromic seed (generic hit words).  The switch is read
-per call, so both kernels run in one process on the same MemHash."""
+per call, so both runs share one process and one MemHash."""
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +23,7 @@ CASES = [
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"G{c[0]}_n{c[1]}_p{c[2]}_w{c[3]}{'_rc' if c[4] else ''}_r{c[5]}")
-def test_walk_refill_matches_oracle(gpu_lib, oracle_mod, monkeypatch, case):
+def test_walks_match_oracle(gpu_lib, oracle_mod, monkeypatch, case):
     G, n, p, w, rc, rank = case
     seqs = oracle_mod.generate(G, n, p, 700 + G)
     if rc:
@@ -35,9 +35,7 @@ def test_walk_refill_matches_oracle(gpu_lib, oracle_mod, monkeypatch, case):
         mh.SetSeed(seed)
         for s in seqs:
             mh.AddSequence(s)
-        for var in ({}, {"MUMS_DEV_WALK_REFILL": "1"}, {"MUMS_DEV_WALK_REFILL": "1", "MUMS_DEV_FIND_CHUNK": "30000"},
-                    {"MUMS_DEV_WALK_SORT": "1"}, {"MUMS_DEV_WALK_SORT": "2"},
-                    {"MUMS_DEV_WALK_SORT": "2", "MUMS_DEV_FIND_CHUNK": "30000"}):
+        for var in ({}, {"MUMS_DEV_FIND_CHUNK": "30000"}):
             with monkeypatch.context() as m:
                 for k, v in var.items():
                     m.setenv(k, v)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of one development switch on the BASELINE config-3 seed stage (bench.py, no
 # FindMatches): VAR=<env name> VALS="0 1 ..." (0 = unset), two repetitions, alternating.
-#   VAR=MUMS_DEV_OS_XCD VALS="0 1" bash tools/ab_env.sh <tag>
+#   VAR=MUMS_DEV_SORT3 VALS="0 3" bash tools/ab_env.sh <tag>
 set -o pipefail
 TAG=${1:-ab_env}
 OUT=gpurun_out/$TAG
