@@ -910,6 +910,12 @@ inline bool seed_bitpar_odd(const SeedSpec& ss) {
     return rev == pat && (ss.w & 1);
 }
 
+// the walks without the generic hit-word path (chains_core); MUMS_DEV_WALK_GEN=1 keeps it
+inline bool walks_lean(const SeedSpec& ss) {
+    const char* gen = getenv("MUMS_DEV_WALK_GEN");
+    return seed_bitpar_odd(ss) && !(gen && gen[0] == '1');
+}
+
 // --- chunked FindMatches: chains labelled per slice of the probes ---------------------
 // launch_chains on a slice of the probes gives every probe its true chain entry (walks
 // read the genomes, not the other probes), but a chain whose probes fall into several
@@ -1125,7 +1131,8 @@ template <int MG, typename LV>
 hipError_t chains_core(LV vl, const ChainWs& w, const uint32_t* ord, uint64_t P, const GenomeTable& gt,
                        const MatchParams& mp, const SeedSpec& ss, const uint32_t* packed, void* d_scan_tmp,
                        uint32_t* chain_of, int64_t* pool, uint32_t* d_nchains, hipStream_t st, void* ctr,
-                       hipEvent_t* ev_walk, uint32_t* fk, uint32_t kbase, uint32_t* jl) {
+                       hipEvent_t* ev_walk, uint32_t* fk, uint32_t kbase, uint32_t* jl, const char* rows_name,
+                       const char* order_name) {
     hipError_t e;
     const unsigned grid = grid_of(P);
     const unsigned walk_grid = 2048, short_grid = 8192;
@@ -1135,7 +1142,10 @@ hipError_t chains_core(LV vl, const ChainWs& w, const uint32_t* ord, uint64_t P,
     const bool cdbg = getenv("MUMS_DEV_CHAIN_DEBUG") != nullptr;
     // the walks without the generic hit-word path when every window is tested by base comparison
     // (palindromic care set, odd weight: hit_word<MG, false>); MUMS_DEV_WALK_GEN=1 keeps it
-    const bool lean = seed_bitpar_odd(ss) && !(getenv("MUMS_DEV_WALK_GEN") && getenv("MUMS_DEV_WALK_GEN")[0] == '1');
+    const bool lean = walks_lean(ss);
+    if (cdbg)   // development: the path of this labelling (the kernels' MG, row view, line order, walk form)
+        fprintf(stderr, "chains: path MG %d P %lu rows %s order %s walks %s\n", MG, (unsigned long)P, rows_name,
+                order_name, lean ? "lean" : "generic");
     for (int pass = 0; pass < 2; ++pass) {
         if ((e = hipMemsetAsync(qcount, 0, 12, st)) != hipSuccess) return e;
         const unsigned lgrid = (unsigned)((P + kBlock * kLinkIPT - 1) / (kBlock * kLinkIPT));
@@ -1211,8 +1221,9 @@ bool chain_line_records(uint64_t P, const GenomeTable& gt) {
 namespace {
 
 hipError_t line_order(const ChainWs& w, uint64_t P, const GenomeTable& gt, void* d_tmp, void* ctr, hipStream_t st,
-                      const uint32_t** ord) {
-    if (chain_line_records(P, gt))
+                      const uint32_t** ord, bool* records) {
+    *records = chain_line_records(P, gt);
+    if (*records)
         return line_sort(w, P, x_bits(gt), d_tmp, ctr ? &((DevCounters*)ctr)->err : w.qcount + 14, st, ord);
     int buf = 0;
     hipError_t e = radix_sort<uint64_t>(w.lkey, nullptr, P, 64, w.kA, w.vA, w.kB, w.vB, d_tmp, &buf, st);
@@ -1292,7 +1303,9 @@ hipError_t launch_chains(View v, const uint64_t* probe_info, uint64_t P, const G
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     const uint32_t* ord = nullptr;
-    if ((e = line_order(w, P, gt, d_radix_tmp, ctr, st, &ord)) != hipSuccess) return e;
+    bool records = false;
+    if ((e = line_order(w, P, gt, d_radix_tmp, ctr, st, &ord, &records)) != hipSuccess) return e;
+    const char* order_name = records ? "records" : "pairs";   // (for MUMS_DEV_CHAIN_DEBUG's path line)
     // the rows in line order: the link / walk / entry kernels then read row j, not row ord[j];
     // as LineRows (int32 starts, 32 B per probe at G = 8) when every start fits 31 bits
     uint64_t mx = 0;
@@ -1313,7 +1326,7 @@ hipError_t launch_chains(View v, const uint64_t* probe_info, uint64_t P, const G
             if (v.rows32) {
                 LineRows vl{v.rows32, v.stride32, v.L32, o};
                 return chains_core<MG>(vl, w, o, P, gt, mp, ss, packed, d_scan_tmp, chain_of, pool, d_nchains, st,
-                                       ctr, ev_walk, fk, kbase, jl);
+                                       ctr, ev_walk, fk, kbase, jl, "int32", order_name);
             }
             if (narrow) {
                 hipLaunchKernelGGL((gather_line_rows_kernel<MG>), dim3(grid_of(P)), dim3(kBlock), 0, st, v.rows, o, P,
@@ -1321,14 +1334,14 @@ hipError_t launch_chains(View v, const uint64_t* probe_info, uint64_t P, const G
                 if ((r = hipGetLastError()) != hipSuccess) return r;
                 LineRows vl{(const int32_t*)w.rows_line, line_row_stride(gt.G), ss.L};
                 return chains_core<MG>(vl, w, o, P, gt, mp, ss, packed, d_scan_tmp, chain_of, pool, d_nchains, st,
-                                       ctr, ev_walk, fk, kbase, jl);
+                                       ctr, ev_walk, fk, kbase, jl, "int32-gathered", order_name);
             }
         }
         if ((r = launch_gather_rows(v.rows, o, P, gt.G, w.rows_line, st)) != hipSuccess) return r;
         MatProbes vl{};
         vl.rows = w.rows_line;
         return chains_core<MG>(vl, w, o, P, gt, mp, ss, packed, d_scan_tmp, chain_of, pool, d_nchains, st, ctr,
-                               ev_walk, fk, kbase, jl);
+                               ev_walk, fk, kbase, jl, "int64", order_name);
     };
     unsigned hf[2] = {0, 0};
     auto read_flags = [&]() -> hipError_t {
@@ -1350,6 +1363,7 @@ hipError_t launch_chains(View v, const uint64_t* probe_info, uint64_t P, const G
     MatProbes vk = v;
     vk.fs = nullptr;
     if ((e = line_order_exact<MG>(vk, w, P, gt, d_radix_tmp, st, &ord)) != hipSuccess) return e;
+    order_name = "exact";
     return chains_from(ord);
 }
 

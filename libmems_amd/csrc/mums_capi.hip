@@ -697,8 +697,10 @@ int materialize_dispatch(mums_ctx* ctx, View sv, const MatchParams& mp, hipStrea
     uint32_t* fs = ctx->fused_keys ? ctx->fsk.as<uint32_t>() : nullptr;
     uint32_t* lh = nullptr;   // the line sort's records and hashes instead of the line keys
     if (ctx->fused_keys && chain_line_records(P, ctx->gt)) chain_line_slots(ctx->chain_tmp.p, P, G, &lk, &lh);
+    const bool cdbg = ctx->fused_keys && getenv("MUMS_DEV_CHAIN_DEBUG");   // development: the one-pass path's row width
     for (int pass = 0; pass < 2; ++pass) {
         int32_t* r32 = narrow ? (int32_t*)rows : nullptr;
+        if (cdbg) fprintf(stderr, "chains: probe rows %s\n", narrow ? "int32" : "int64");
         if (narrow) HIPCHK(hipMemsetAsync(fs + P, 0, 4, st));
         if (G <= 4) HIPCHK((launch_materialize<4, View>(sv, ctx->probe_info, P, ctx->gt, mp, ctx->L, rows, st, lk, fs, lh, r32)));
         else if (G <= 8) HIPCHK((launch_materialize<8, View>(sv, ctx->probe_info, P, ctx->gt, mp, ctx->L, rows, st, lk, fs, lh, r32)));

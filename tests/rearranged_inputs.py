@@ -258,10 +258,14 @@ def stretches(oracle, name):
     of columns inside the match in its reference genome -- the first defined component, always
     forward --, probes left of it, probes right of it)."""
     seqs, seed, lengths, starts, _ = oracle_result(oracle, name)
-    xlen = CASES[name][1]["xlen"]
-    per_genome = probe_positions(oracle, seqs, seed)
+    return stretches_of(oracle, seqs, seed, lengths, starts, CASES[name][1]["xlen"])
+
+
+def stretches_of(oracle, seqs, seed, lengths, starts, min_len, table_size=40000):
+    """stretches() of any MatchList: the matches of length >= min_len."""
+    per_genome = probe_positions(oracle, seqs, seed, table_size)
     out = []
-    for i in np.nonzero(lengths >= xlen)[0]:
+    for i in np.nonzero(lengths >= min_len)[0]:
         g = int(np.argmax(starts[i] != 0))
         s0 = int(starts[i, g])
         assert s0 > 0   # SetDirection: the first defined component is forward

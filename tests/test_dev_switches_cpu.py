@@ -67,6 +67,17 @@ def test_tests_named_in_the_table_set_the_switch():
             assert re.search(name + r"\b", open(os.path.join(ROOT, "tests", t)).read()), (name, t)
 
 
+def test_product_paths_and_alternatives_have_a_test():
+    """A switch that forces a product path or selects an alternative implementation exists to be
+    set by a test: only a diagnostics row may say "no test"."""
+    text = open(os.path.join(ROOT, "DESIGN.md")).read()
+    rows = re.findall(r"^\|\s*`(MUMS_DEV_[A-Z0-9_]+)`\s*\|\s*([^|]*?)\s*\|[^|]*\|\s*([^|]*?)\s*\|$", text, re.M)
+    assert len(rows) == len(_table_names())
+    untested = [name for name, kind, test in rows if kind != "diagnostics" and not re.findall(r"`[^`]+\.py`", test)]
+    assert not untested, untested
+    assert not [name for name, kind, test in rows if "no test" in test and kind != "diagnostics"]
+
+
 def test_pruned_variants_stay_out():
     where = _files("libmems_amd/**", "include/**", "tests/*.py", "tools/*.py", "tools/*.sh", "tools/*.cpp",
                    "tools/dev/**")

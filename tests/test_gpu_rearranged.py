@@ -72,13 +72,15 @@ def test_modes(gpu_lib, oracle_mod, name):
 
 
 def path_variants(chunk):
-    """test_gpu_row_paths.VARIANTS with this case's slice size, plus the line order forced exact,
-    the walks' generic hit words and the big-bucket replay forced onto small buckets (the values
-    of test_gpu_replay_big.py)."""
+    """test_gpu_row_paths.VARIANTS with this case's slice size, plus the line order forced exact
+    or onto the pair sort, the walks' generic hit words and the big-bucket replay forced onto
+    small buckets (the values of test_gpu_replay_big.py)."""
     out = [{k: (str(chunk) if k == "MUMS_DEV_FIND_CHUNK" else v) for k, v in var.items()} for var in VARIANTS]
     out += [{"MUMS_DEV_LINE_EXACT": "1"}, {"MUMS_DEV_WALK_GEN": "1"},
             {"MUMS_DEV_BIG_BUCKET": "8"}, {"MUMS_DEV_BIG_BUCKET": "8", "MUMS_DEV_GRID_SLOW": "0"},
-            {"MUMS_DEV_LINE_EXACT": "1", "MUMS_DEV_FIND_CHUNK": str(chunk)}]
+            {"MUMS_DEV_LINE_EXACT": "1", "MUMS_DEV_FIND_CHUNK": str(chunk)},
+            # the line order by the 64-bit pair sort (the full product: test_gpu_chain_paths.py)
+            {"MUMS_DEV_LINE_RADIX": "1"}, {"MUMS_DEV_LINE_RADIX": "1", "MUMS_DEV_FIND_CHUNK": str(chunk)}]
     return out
 
 
