@@ -398,6 +398,9 @@ public:
     // pass per list of rounds (mums_recursion_batch): per problem Clear; per weight of
     // recursion_rounds ClearSequences + FindMatches on all G sequences into one table;
     // EliminateOverlaps (v1); MultiplicityFilter(G) when nway_only; LengthFilter(min_length).
+    // The finder is this object: the reference uses gap_mh (MemHash), and under nway_only nway_mh,
+    // a MaskedMemHash whose mask selects every genome (Aligner.h:199, Aligner.cpp:1190-1195,
+    // 2208-2212): make an nway_only call on a MaskedMemHash with SetMask((1 << G) - 1).
     // weights empty: getDefaultSeedWeight(length) per sequence; else per problem its G weights.  A
     // problem without a round gets an empty list and no search.  AnchorBatchInfo() has the counters.
     virtual void RecursionBatch(const std::vector<std::vector<std::string>>& problems, std::vector<MatchList>& out,

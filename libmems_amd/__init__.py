@@ -665,8 +665,12 @@ class MemHash:
         device pass per list of rounds (mums_recursion_batch): per problem Clear; per seed weight of
         recursion_rounds(its lengths, nway_only) ClearSequences + FindMatches on all G sequences
         into one table; EliminateOverlaps (v1); MultiplicityFilter(G) when nway_only;
-        LengthFilter(min_length) (MIN_ANCHOR_LENGTH = 9).  problems: G-tuples of bytes, the same G
-        for all; weights: per problem its sequences' seed weights instead of the defaults.  A
+        LengthFilter(min_length) (MIN_ANCHOR_LENGTH = 9).  The finder is this object: the reference
+        searches with gap_mh, a MemHash, and under nway_only with nway_mh, a MaskedMemHash whose
+        mask selects every genome (Aligner.h:199, Aligner.cpp:1190-1195, 2208-2212), so an
+        nway_only call belongs on a MaskedMemHash with SetMask((1 << G) - 1); on a MemHash the
+        subset seeds are hashed too and can crop n-way matches before the filter drops them.
+        problems: G-tuples of bytes, the same G for all; weights: per problem its sequences' seed weights instead of the defaults.  A
         problem without a round gets an empty list and no device work.  The below_cutoff_count gate
         (:1136) is the caller's.  Returns one MatchList per problem with starts in the problem's own
         sequences; RecursionBatchInfo() has every problem's counters."""

@@ -15,8 +15,10 @@
  * _S_threshold 16 and depth 2*lg(n), __move_median_to_first, __unguarded_partition,
  * __partial_sort = heap select + sort_heap, __final_insertion_sort); tests pin it against
  * the real std::sort of this toolchain (tests/eo_model.cpp).  Parity of EliminateOverlaps
- * itself is unpinned by reference fixtures (the reference has none and Aligner.cpp needs
- * libGenome / MUSCLE to build).
+ * itself is pinned by tests/golden/ref_cases.json: the eo1 and recursion cases were recorded
+ * from the reference's own function (Aligner.cpp:62-176, extracted at build time into
+ * oracle/_ref/ and run by oracle/ref_driver.cpp), and tests/test_ref_pinning_cpu.py holds this
+ * file to them row for row.
  */
 #include <stdint.h>
 #include <stdlib.h>

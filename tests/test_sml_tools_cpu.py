@@ -1,7 +1,7 @@
 """CPU checks of the oracle's SeedOccurrenceList restatement (SeedOccurrenceList.h:22-87)
-against a pure-Python transcription of the same loops over the oracle's SML.  No
-reference fixture covers SeedOccurrenceList: parity for this row is unpinned beyond the
-shared SML construction (the oracle's SML is pinned through the Appendix C md5s)."""
+against a pure-Python transcription of the same loops over the oracle's SML.  The
+reference's own SeedOccurrenceList::construct pins the oracle on the occurrence cases of
+tests/golden/ref_cases.json (test_ref_pinning_cpu.py)."""
 import numpy as np
 import pytest
 
